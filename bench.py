@@ -8,8 +8,19 @@ One step = one pass of the whole receive chain (Schmidl-Cox + plateau, access-co
 estimate, detector weights, replay decode, demap, EVM) over a batch of synthetic captures
 already resident in HBM. Symbol errors and EVM are counted against the transmitted QAM indices
 read from HBM (--ref-mode 1), as main.cc compares with its tx_data file (main.cc:1394-1411).
-Repeated steps replay a captured HIP graph of the batch; per-stage times come from a separate
-pass with event timing (direct launches).
+Repeated steps replay a captured HIP graph of the batch.
+
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs if asked and prints
+the result line. --full adds every secondary measurement to that line: per-stage times from a
+separate pass with event timing (direct launches) and the decode roofline built on them, the
+decode memory-pattern probe, the sc16-resident leg, the rank-0 scatter leg (N > 1), the
+pipeline's serial comparison, the CPU oracle baseline with its EVM delta, and the H2D copy
+rate. Without --full those fields are null.
+
+--dump-outputs DIR writes what the last timed step left in the caller's buffers as float
+.npy files: a fixed seeded sample of the equalised symbols (out_sym.npy, [n][re, im]) and of
+the demapped indices (out_idx.npy) at the same positions, zero where a slot did not decode or
+the symbol lies past the frame's end, and the per-slot results (frame_*.npy).
 
 `value` counts the samples of the frames that reach the detector (status OK) per second;
 captures that never sync are scanned (S&C) but not detected and only count toward the
@@ -23,8 +34,8 @@ ingest path: rank 0 holds every rank's captures at the sc16 wire format and scat
 RCCL point-to-point (double-buffered against the receive; rub_mimo_amd/shard.py), reported
 under `rank0_scatter`; `--ingest scatter` makes that the timed mode.
 
-Prints one JSON line (rank 0) with the roofline of the dominant kernel (decode) and the CPU
-oracle baseline measured on this host (1 core and the box's core share).
+Prints one JSON line (rank 0); with --full it carries the roofline of the dominant kernel
+(decode) and the CPU oracle baseline measured on this host (1 core and the box's core share).
 """
 import argparse
 import ctypes
@@ -77,11 +88,17 @@ def parse():
         ap.add_argument("--" + k, type=t, default=None)
     ap.add_argument("--detector", default=None, choices=["zf2", "zf", "mmse"])
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (stage times and roofline, "
+                         "pattern probe, sc16 and scatter legs, CPU baseline, H2D)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy")
     ap.add_argument("--ingest", default="resident", choices=["resident", "scatter"],
                     help="resident: each rank's captures already in its HBM (headline); "
                          "scatter: rank 0 scatters sc16 wire captures every step (timed)")
     ap.add_argument("--scatter-steps", type=int, default=5,
-                    help="steps of the secondary rank-0 scatter leg when N > 1 (0: skip)")
+                    help="--full: steps of the secondary rank-0 scatter leg when N > 1 "
+                         "(0: skip)")
     ap.add_argument("--cfo", type=float, default=0.0,
                     help="apply this carrier-frequency offset (subcarrier spacings) to the "
                          "synthetic captures and turn on the receiver's opt-in CFO correction")
@@ -89,11 +106,13 @@ def parse():
                     help="resident capture format: fc32 (complex64, the reference's framesync "
                          "input) or sc16 (UHD wire samples read in place, 4 B/sample)")
     ap.add_argument("--sc16-steps", type=int, default=None,
-                    help="steps of the secondary sc16-resident leg of an fc32 run (0: skip; "
-                         "default: --steps)")
-    ap.add_argument("--cpu-baseline", type=int, default=1, help="0 to skip the oracle timing")
+                    help="--full: steps of the secondary sc16-resident leg of an fc32 run "
+                         "(0: skip; default: --steps)")
+    ap.add_argument("--cpu-baseline", type=int, default=1,
+                    help="--full: 0 to skip the oracle timing")
     ap.add_argument("--h2d", type=int, default=1,
-                    help="0 to skip the separately reported pinned-host -> HBM copy timing")
+                    help="--full: 0 to skip the separately reported pinned-host -> HBM copy "
+                         "timing")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="threads of the multi-core CPU baseline (0: the box's core share)")
     ap.add_argument("--out-layout", default="symbol", choices=["symbol", "stream"],
@@ -109,6 +128,8 @@ def parse():
                          "beside batch i+1's front stages (S&C .. weights) on the other CUs "
                          "(CU-masked HIP streams, mimo_batch.stages); 0: one serial stream")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     w = WORKLOADS[a.workload]
     for k in ("M", "cp", "streams", "nac", "pid", "qam", "snr", "detector", "frames"):
         if getattr(a, k) is None:
@@ -181,6 +202,45 @@ def decode_kernel_name(M, N, args, path=None):
     if N == 8 and 512 <= M <= 4096 and args.detector != "siso" and args.pid >= M // 64:
         return "spectra_kernel<%d>|apply_split_kernel<8>" % lg
     return "decode_kernel<%d,%d>" % (lg, N)
+
+
+DUMP_SAMPLE = 1 << 21    # sampled positions of out_sym / out_idx (24 MB of float32 in all)
+
+
+def dump_outputs(path, rank, res, out_sym, out_idx, pid, N, m_occ, sym_major, ok_status):
+    """--dump-outputs: what the last timed step left for the caller, as float .npy files."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    tag = "" if rank == 0 else "_rank%d" % rank
+    total = out_sym.numel()
+    if total <= DUMP_SAMPLE:
+        pos = np.arange(total, dtype=np.int64)
+    else:
+        pos = np.sort(np.random.default_rng(0).integers(0, total, DUMP_SAMPLE, dtype=np.int64))
+    dpos = torch.from_numpy(pos).to(out_sym.device)
+    sym = torch.view_as_real(out_sym.reshape(-1)[dpos]).cpu().numpy().astype(np.float32)
+    idx = out_idx.reshape(-1)[dpos].cpu().numpy().astype(np.float32)
+    # positions the receive never wrote (slot not decoded, symbol past the frame's end) hold
+    # whatever the allocation held: zero them so that two runs compare
+    okf = np.array([r["status"] == ok_status for r in res])
+    n_sym = np.array([min(int(r["n_sym"]), pid) for r in res], np.int64)
+    slot = pos // (pid * N * m_occ)
+    symbol = (pos // (N * m_occ)) % pid if sym_major else (pos // m_occ) % pid
+    dead = ~(okf[slot] & (symbol < n_sym[slot]))
+    sym[dead] = 0
+    idx[dead] = 0
+    np.save(os.path.join(path, "out_sym%s.npy" % tag), sym)
+    np.save(os.path.join(path, "out_idx%s.npy" % tag), idx)
+
+    def per_slot(key, live_only=True):
+        a = np.array([np.asarray(r[key], np.float64) for r in res], np.float64)
+        if live_only:
+            a[~okf] = 0
+        np.save(os.path.join(path, "frame_%s%s.npy" % (key, tag)), a)
+
+    per_slot("status", False)
+    for key in ("n_sym", "sync_index", "origin", "evm_num", "evm_den", "errors"):
+        per_slot(key)
 
 
 def cpu_model():
@@ -405,6 +465,7 @@ def main():
 
     timed_scatter = args.ingest == "scatter"
     pipe_info = None
+    rx_last = rx        # the handle whose results and buffers the last timed step filled
     if args.pipeline and (timed_scatter or args.cfo or c5):
         raise SystemExit("--pipeline: resident one-frame-per-capture batches without --cfo only")
     if args.pipeline:
@@ -450,22 +511,13 @@ def main():
             pstep(i + 2 * max(args.warmup, 2))
         torch.cuda.synchronize(dev)
         elapsed = time.perf_counter() - t0
-        # the serial step of the same batch on the whole chip, for the line
-        for _ in range(2):
-            step()
-        torch.cuda.synchronize(dev)
-        t1 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        torch.cuda.synchronize(dev)
+        rx_last = hs[(args.steps - 1) & 1]      # the handle that ran the last timed batch
         pipe_info = {"decode_cus": D, "front_cus": n_cu_dev - D,
-                     "serial_ms_per_step": (time.perf_counter() - t1) / args.steps * 1e3,
+                     "serial_ms_per_step": None,
                      "note": "batch i's decode (mimo_batch.stages = DECODE) on D CUs beside "
                              "batch i+1's S&C, search, LS and weights (stages = FRONT) on the "
-                             "others; two handles alternate batches; serial_ms_per_step is the "
-                             "whole chain on the whole chip, one stream"}
-        hs[0].results(F * K)
-        del hs
+                             "others; two handles alternate batches; serial_ms_per_step "
+                             "(--full) is the whole chain on the whole chip, one stream"}
     elif timed_scatter:
         wire = make_wire()
         pipe = ScatterPipeline(dist if world > 1 else None, wire, (F, N, L, 2), torch.int16, dev,
@@ -491,17 +543,40 @@ def main():
         if world > 1:
             dist.barrier()
         elapsed = time.perf_counter() - t0
-    n_exact = rx.sc_exact_count()
-    # per-stage HIP-event times (roofline numerator/denominator) from a separate pass over the
-    # same workload: event timing runs the launches directly instead of the captured graph
+    # ---- what the last timed step computed
+    res = rx_last.results(F * K)
+    dec_path = rx_last.decode_path()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, res, out_sym, out_idx, pid, N, m_occ, sym_major,
+                     _lib.FRAME_OK)
+    if args.pipeline:
+        n_exact = sum(h.sc_exact_count() for h in hs)
+        del hs, rx_last
+        if args.full:
+            # the serial step of the same batch on the whole chip, for the line
+            for _ in range(2):
+                step()
+            torch.cuda.synchronize(dev)
+            t1 = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            torch.cuda.synchronize(dev)
+            pipe_info["serial_ms_per_step"] = (time.perf_counter() - t1) / args.steps * 1e3
+            n_exact = rx.sc_exact_count()
+    else:
+        n_exact = rx.sc_exact_count()
+    # --full: per-stage HIP-event times (roofline numerator/denominator) from a separate pass
+    # over the same workload: event timing runs the launches directly instead of the captured
+    # graph
+    stages = None
     n_stage = max(1, min(args.steps, 5))
-    rx.set_timing(True)
-    for _ in range(n_stage):
-        step()
-    torch.cuda.synchronize(dev)
-    rx.set_timing(False)
-    stages = rx.stage_times()
-    res = rx.results(F * K)
+    if args.full:
+        rx.set_timing(True)
+        for _ in range(n_stage):
+            step()
+        torch.cuda.synchronize(dev)
+        rx.set_timing(False)
+        stages = rx.stage_times()
     ok_slots = [i for i, r in enumerate(res) if r["status"] == _lib.FRAME_OK]
     ok = len(ok_slots)
     rescans = sum(1 for r in res if r["status"] == _lib.FRAME_RESCAN)
@@ -536,7 +611,7 @@ def main():
     # read in place (C3-type geometries) or widened internally; its own EVM (quantised input)
     sc16_info = None
     n16 = args.steps if args.sc16_steps is None else args.sc16_steps
-    if not sc16 and not timed_scatter and n16 > 0 and not args.cfo:
+    if args.full and not sc16 and not timed_scatter and n16 > 0 and not args.cfo:
         w16 = (torch.view_as_real(iq) / wscale).round_().clamp_(-32768, 32767).to(torch.int16)
         for _ in range(2):
             step(w16, True)
@@ -570,7 +645,7 @@ def main():
 
     # ---- secondary leg (N > 1, resident headline): rank-0 sc16 scatter, bounded
     scatter_info = None
-    if world > 1 and not timed_scatter and args.scatter_steps > 0:
+    if args.full and world > 1 and not timed_scatter and args.scatter_steps > 0:
         wire = make_wire()
         pipe = ScatterPipeline(dist, wire, (F, N, L, 2), torch.int16, dev, rank, world)
         scatter_loop(pipe, 1)
@@ -589,22 +664,22 @@ def main():
         del wire
 
     # ---- roofline of the dominant kernel: decode (HBM bound)
-    dec_ms, dec_n = stages["decode"]
+    dec_ms, dec_n = stages["decode"] if stages else (0.0, 0)
     dec_avg_s = dec_ms / max(dec_n, 1) / 1e3
     # per decoded symbol: N bodies read, N x M_occ complex64 + uint8 written (+ the uint8
     # transmitted index read when the EVM reference comes from HBM)
-    kname = decode_kernel_name(M, N, args, rx.decode_path())
+    kname = decode_kernel_name(M, N, args, dec_path)
     # (sc16 is read in place by the streaming decode; other decode kernels read the widened copy)
     dec_in = in_bytes if kname.startswith("decode_stream") else 8
     per_sym = N * M * dec_in + N * m_occ * 9 + (N * m_occ if args.ref_mode == 1 else 0)
     dec_bytes = n_dec * per_sym
-    achieved = dec_bytes / dec_avg_s / 1e9 if dec_avg_s > 0 else 0.0
+    achieved = dec_bytes / dec_avg_s / 1e9 if dec_avg_s > 0 else (0.0 if stages else None)
     # ---- the decode's memory pattern alone, on this box, in this process (after the timed
     # region): mimo_probe_decode_pattern stages and stores exactly the decode's bytes on its
     # grid with no arithmetic, over the same buffers -- the rate this box's HBM gives that
     # pattern, against which the decode's own time is stated
     pattern = None
-    if (kname.startswith("decode_stream") and not c5 and not sc16 and not args.cfo
+    if (args.full and kname.startswith("decode_stream") and not c5 and not sc16 and not args.cfo
             and args.ref_mode == 1 and sym_major and m_occ == M and ok > 0
             and (N, M) in ((4, 2048), (4, 1024), (2, 4096), (2, 2048), (2, 1024))):
         pms = ctypes.c_float(0.0)
@@ -637,7 +712,7 @@ def main():
     # ---- CPU baseline: the C oracle on synced frames of this batch (rank 0, N = 1 only)
     cpu = None
     evm_delta = None
-    if rank == 0 and world == 1 and args.cpu_baseline and ok_slots:
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline and ok_slots:
         from oracle import ref
         sel = ok_slots[:4]
         frames = []
@@ -664,7 +739,7 @@ def main():
     # ---- H2D, reported separately (never the headline): the batch's captures
     # copied from pinned host memory into HBM on the receive stream, at most 8 captures
     h2d = None
-    if rank == 0 and args.h2d:
+    if args.full and rank == 0 and args.h2d:
         nc = min(F, 8)
         dev_iq = iq[:nc]
         host = torch.empty(dev_iq.shape, dtype=dev_iq.dtype, pin_memory=True)
@@ -696,6 +771,7 @@ def main():
         "unit": "complex samples/s",
         "n_gpus": world,
         "steps": args.steps,
+        "full": bool(args.full),
         "warmup": args.warmup,
         "ms_per_step": ms_step,
         "higher_is_better": True,
@@ -717,10 +793,11 @@ def main():
                    "parallelism": ("%d streams over %d GPU(s)" % (args.frames, world) if c5 else
                                    "frames sharded across %d GPU(s), no collective" % world)},
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                     "unit": "GB/s",
+                     "frac": achieved / HBM_PEAK_GBS if stages else None, "traffic": traffic,
                      "kernel": kname, "bytes_per_launch": dec_bytes,
                      "symbols_per_launch": n_dec, "bytes_per_symbol": per_sym,
-                     "avg_launch_ms": dec_avg_s * 1e3},
+                     "avg_launch_ms": dec_avg_s * 1e3 if stages else None},
         "decode_pattern_ms": pattern["ms"] if pattern else None,
         "decode_vs_pattern": pattern["decode_vs_pattern"] if pattern else None,
         "decode_pattern": pattern,
@@ -729,7 +806,8 @@ def main():
         "evm_db_delta_vs_cpu": evm_delta,
         "scan_rate_all_captures": scanned_total / elapsed,
         "pipeline_hbm_gbs": bytes_alg / elapsed / 1e9,
-        "stages_ms_per_step": {k: v[0] / n_stage for k, v in stages.items()},
+        "stages_ms_per_step": ({k: v[0] / n_stage for k, v in stages.items()} if stages
+                               else None),
         "frames_ok": int(ok_all),
         "frames": int(args.frames * args.frames_per_stream) if c5 else int(F * world),
         "rescan_slots": rescans,
@@ -741,7 +819,8 @@ def main():
         # FFT + detect + demap + EVM given W (the decode stage alone), samples of the decoded
         # symbols (N antennas x (M + cp)) per second of the decode kernels' event time
         "decode_stage": {"value": (n_dec * N * (M + cp) / dec_avg_s) if dec_avg_s > 0 else None,
-                         "unit": "complex samples/s", "ms_per_step": dec_avg_s * 1e3,
+                         "unit": "complex samples/s",
+                         "ms_per_step": dec_avg_s * 1e3 if stages else None,
                          "symbols_per_step": n_dec},
         "h2d": h2d,
     }

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 timeout -k 10 300 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread -k "cfo" > $O/cfo_tests.log 2>&1 || { echo "cfo tests failed"; tail -n 30 $O/cfo_tests.log; exit 1; }
 tail -n 1 $O/cfo_tests.log
 for v in 0 0.3; do
-  timeout -k 10 200 python bench.py --cfo $v --cpu-baseline 0 --sc16-steps 0 --h2d 0 > $O/bench_cfo_$v.json 2> $O/bench_cfo_$v.err || { echo "bench failed"; tail -20 $O/bench_cfo_$v.err; exit 1; }
+  timeout -k 10 200 python bench.py --full --cfo $v --cpu-baseline 0 --sc16-steps 0 --h2d 0 > $O/bench_cfo_$v.json 2> $O/bench_cfo_$v.err || { echo "bench failed"; tail -20 $O/bench_cfo_$v.err; exit 1; }
   python3 -c "
 import json; d=json.load(open('$O/bench_cfo_$v.json'))
 print('cfo $v', 'value %.4g'%d['value'], 'ms %.4f'%d['ms_per_step'], 'ok %d'%d['frames_ok'], 'evm %.3f'%d['evm_db'], {k:round(x,4) for k,x in d['stages_ms_per_step'].items()})"

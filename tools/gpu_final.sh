@@ -9,9 +9,9 @@ mkdir -p $O
 cd $R
 timeout -k 10 500 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $O/gpu_tests.log 2>&1 || { echo "gpu tests failed"; tail -30 $O/gpu_tests.log; exit 1; }
 tail -1 $O/gpu_tests.log
-timeout -k 10 300 python bench.py > $O/bench_c3.json 2> $O/bench_c3.err || { echo "bench c3 failed"; tail -20 $O/bench_c3.err; exit 1; }
+timeout -k 10 300 python bench.py --full > $O/bench_c3.json 2> $O/bench_c3.err || { echo "bench c3 failed"; tail -20 $O/bench_c3.err; exit 1; }
 for w in c2 c4 c5; do
-  timeout -k 10 200 python bench.py --workload $w --cpu-baseline 0 > $O/bench_$w.json 2> $O/bench_$w.err || { echo "bench $w failed"; tail -20 $O/bench_$w.err; exit 1; }
+  timeout -k 10 200 python bench.py --full --workload $w --cpu-baseline 0 > $O/bench_$w.json 2> $O/bench_$w.err || { echo "bench $w failed"; tail -20 $O/bench_$w.err; exit 1; }
 done
 export PMC_KERNEL="decode|spectra|apply_split"
 for w in c3 c4; do

@@ -11,7 +11,7 @@ if [ -n "${TESTS+x}" ]; then
   tail -n 2 $O/gpu_tests.log
 fi
 for w in ${WORKLOADS:-c3}; do
-  timeout -k 10 200 python bench.py --workload $w --cpu-baseline 0 $BENCH_ARGS > $O/bench_$w.json 2> $O/bench_$w.err || { echo "bench $w failed"; tail -n 20 $O/bench_$w.err; exit 1; }
+  timeout -k 10 200 python bench.py --full --workload $w --cpu-baseline 0 $BENCH_ARGS > $O/bench_$w.json 2> $O/bench_$w.err || { echo "bench $w failed"; tail -n 20 $O/bench_$w.err; exit 1; }
   python -c "
 import json; d=json.load(open('$O/bench_$w.json'))
 print('$w', 'value %.4g'%d['value'], 'ms %.4f'%d['ms_per_step'], 'ok %d/%d'%(d['frames_ok'],d['frames']), 'roof %.3f'%d['roofline']['frac'], d['roofline']['kernel'], 'evm %.3f'%d['evm_db'])
