@@ -209,6 +209,50 @@ int mimo_rx_batch_corr(mimo_rx *h, uint32_t *corr_idx, uint32_t *s0_idx, uint32_
 int mimo_rx_batch_G(mimo_rx *h, float *G, uint32_t n_frames);
 int mimo_rx_batch_W(mimo_rx *h, float *W, uint32_t n_frames);
 
+/* ---------------- soft output (absent from the reference: main.cc slices to a hard index) ----
+ * An opt-in pass after mimo_rx_process_batch (MIMO_STAGES_ALL or _DECODE) over that batch's
+ * equalised symbols; the batch itself launches nothing for it. Both calls read the handle's G,
+ * W, gain and per-frame noise variance of the batch it last ran; they work with cfo_correct
+ * and with frames_per_capture > 1 (frame slots as mimo_rx_batch_results counts them).
+ *
+ * Post-detection MSE of output stream t on occupied carrier j (subcarrier k) of frame f, the
+ * predicted E|y_t - s_t|^2 for X = G s + n, n ~ CN(0, s2 I), s2 = the frame's noise_var, and the
+ * decode's y_t = g_k sum_r W[t][r] X_r:
+ *   nu[f][t][j] = g_k^2 s2 sum_r |W[t][r]|^2 + sum_u |g_k sum_r W[t][r] G[r][u] - delta_tu|^2
+ * (noise enhancement, plus residual inter-stream interference and the MMSE bias as noise).
+ *
+ * Max-log LLRs of a square Gray QAM of order L^2, b = log2 L bits per dimension, 2b values per
+ * symbol: value i belongs to bit i of the demapped index counted from its most significant bit
+ * (the index is (gray(mI) << b) | gray(mQ)), so values 0..b-1 depend on Re y and b..2b-1 on
+ * Im y. With levels l_m = (2m - (L-1)) scale and x the part of y the bit depends on,
+ *   LLR_i = llr_scale (min_{m: bit_i(gray m) = 1} (x - l_m)^2
+ *                      - min_{m: bit_i(gray m) = 0} (x - l_m)^2) / max(nu, 1e-30)
+ * positive = bit 0 more likely, taken on y as delivered (not unbiased), so a non-zero LLR's
+ * sign is the matching bit of d_out_idx. MIMO_LLR_F32 stores the value, MIMO_LLR_I8
+ * clamp(rintf(value), -127, 127) (round half to even). A NaN y gives 0, and so does every row
+ * the decode does not write (frames with status != MIMO_FRAME_OK, symbols >= min(n_sym,
+ * max_out_syms)): the whole d_llr is defined after the call.
+ *
+ * MIMO_DET_SISO returns MIMO_ERR_UNSUPPORTED: the handle's W is not the SISO weight
+ * (the SISO decode divides by G[rx][tx]), and one stream's LLRs are left to a later change. */
+enum { MIMO_LLR_I8 = 0, MIMO_LLR_F32 = 1 };
+typedef struct mimo_soft_demap {
+  const void *d_sym;      /* the last batch's d_out_sym (same out_layout, max_out_syms) */
+  void *d_llr;            /* [d_out_sym's rows][M_occ][2b] int8 or float */
+  uint32_t n_frames;      /* frame slots, as mimo_rx_batch_results counts them */
+  uint32_t max_out_syms;
+  uint32_t out_layout;    /* MIMO_LAYOUT_* of d_sym; d_llr follows it */
+  uint32_t format;        /* MIMO_LLR_* */
+  float llr_scale;        /* finite, > 0 */
+} mimo_soft_demap;
+/* Asynchronous on hip_stream (NULL: the handle's), no host synchronisation; the caller orders
+ * it after the batch that wrote d_sym. Allocates only when the slot count grows, so it can be
+ * captured into a graph after one warm-up call. d_sym and d_llr 16-byte aligned; n_frames and
+ * max_out_syms must equal the last batch's (MIMO_ERR_ARG); MIMO_ERR_STATE before any batch. */
+int mimo_rx_soft_demap(mimo_rx *h, const mimo_soft_demap *a, void *hip_stream);
+/* host copy of nu, [n_frames][N][M_occ] floats; rows of unsynced slots are 0; synchronises */
+int mimo_rx_batch_mse(mimo_rx *h, float *mse, uint32_t n_frames);
+
 /* stage timing with HIP events on the handle's launch stream (for the roofline line).
  * stages: 0 S&C, 1 plateau, 2 search, 3 LS, 4 weights, 5 decode, 6 EVM reduce; an sc16 batch
  * that is widened internally (not read in place) adds its widening launch to stage 0 */

@@ -26,6 +26,8 @@ DECODE_NONE, DECODE_STREAM, DECODE_SPLIT, DECODE_SYMBOL = 0, 1, 2, 3
 LAYOUT_STREAM_MAJOR, LAYOUT_SYMBOL_MAJOR = 0, 1
 # mimo_batch.stages: the whole chain, the front half (S&C .. weights) or the decode half
 STAGES_ALL, STAGES_FRONT, STAGES_DECODE = 0, 1, 2
+# mimo_soft_demap.format: int8 (rounded, clamped to +-127) or fp32 LLRs
+LLR_I8, LLR_F32 = 0, 1
 
 
 class RxConfig(C.Structure):
@@ -46,6 +48,12 @@ class Batch(C.Structure):
                 ("frames_per_capture", C.c_uint32), ("ref_stride", C.c_uint32),
                 ("d_ref_starts", C.c_void_p), ("sample_format", C.c_uint32),
                 ("sc16_scale", C.c_float), ("out_layout", C.c_uint32), ("stages", C.c_uint32)]
+
+
+class SoftDemap(C.Structure):
+    _fields_ = [("d_sym", C.c_void_p), ("d_llr", C.c_void_p), ("n_frames", C.c_uint32),
+                ("max_out_syms", C.c_uint32), ("out_layout", C.c_uint32),
+                ("format", C.c_uint32), ("llr_scale", C.c_float)]
 
 
 class FrameResult(C.Structure):
@@ -93,6 +101,8 @@ SIGNATURES = {
     "mimo_rx_batch_corr": (C.c_int, [_vp, _vp, _vp, _u32]),
     "mimo_rx_batch_G": (C.c_int, [_vp, _vp, _u32]),
     "mimo_rx_batch_W": (C.c_int, [_vp, _vp, _u32]),
+    "mimo_rx_soft_demap": (C.c_int, [_vp, _P(SoftDemap), _vp]),
+    "mimo_rx_batch_mse": (C.c_int, [_vp, _vp, _u32]),
     "mimo_rx_set_timing": (C.c_int, [_vp, C.c_int]),
     "mimo_rx_get_stage_times": (C.c_int, [_vp, _P(C.c_double), _P(_u32)]),
     "mimo_rx_get_sc_exact_count": (C.c_int, [_vp, _P(_u64)]),

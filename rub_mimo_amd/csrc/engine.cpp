@@ -248,6 +248,7 @@ struct mimo_rx {
   uint32_t last_frames = 0, last_max_out = 0;
   int last_decode_path = MIMO_DECODE_NONE;   // kernel family of the last decode launch
   int last_cfo_mode = 0;                     // CFO stages of the last batch (get_cfo_mode)
+  DevBuf<float> nu;                          // soft output: post-detection MSE [F][N][M_occ]
   // streaming state (facade). The device capture holds samples [origin, origin + total) of
   // the stream since construction/reset (positions inside it are capture-relative).
   DevBuf<float2> capbuf;
@@ -1662,6 +1663,74 @@ int mimo_rx_batch_W(mimo_rx *h, float *W, uint32_t F) {
     int rc = copy_W(h, f, W + (size_t)f * h->M * h->N * h->N * 2);
     if (rc) return rc;
   }
+  return MIMO_OK;
+}
+
+// ---------------- soft output: post-detection MSE and max-log LLRs (soft_kernels.hip) -------
+// the MSE of the last batch's F frame slots into h->nu, on stream s
+static int launch_batch_mse(mimo_rx *h, uint32_t F, hipStream_t s) {
+  if (h->nu.ensure((size_t)F * h->N * h->M_occ) != hipSuccess)
+    return fail(MIMO_ERR_NOMEM, "post-detection MSE buffer");
+  MseArgs m{};
+  m.N = h->N; m.M = h->M; m.M_occ = h->M_occ;
+  m.occ_index = h->occ.p; m.G = h->G.p; m.W = h->W.p; m.gain = h->gain.p; m.info = h->info.p;
+  m.nu = h->nu.p;
+  if (!launch_mse(m, F, s)) return fail(MIMO_ERR_UNSUPPORTED, "no MSE kernel for this stream count");
+  HIPCHK(hipGetLastError());
+  return MIMO_OK;
+}
+
+int mimo_rx_soft_demap(mimo_rx *h, const mimo_soft_demap *a, void *hip_stream) {
+  if (!h || !a || !a->d_sym || !a->d_llr) return fail(MIMO_ERR_ARG, "null argument");
+  if (((uintptr_t)a->d_sym & 15u) || ((uintptr_t)a->d_llr & 15u))
+    return fail(MIMO_ERR_ARG, "d_sym and d_llr must be 16-byte aligned");
+  if (!std::isfinite(a->llr_scale) || !(a->llr_scale > 0.0f))
+    return fail(MIMO_ERR_ARG, "llr_scale must be finite and positive");
+  if (a->format != MIMO_LLR_I8 && a->format != MIMO_LLR_F32)
+    return fail(MIMO_ERR_ARG, "mimo_soft_demap.format must be MIMO_LLR_I8 or _F32");
+  if (a->out_layout != MIMO_LAYOUT_STREAM_MAJOR && a->out_layout != MIMO_LAYOUT_SYMBOL_MAJOR)
+    return fail(MIMO_ERR_ARG, "mimo_soft_demap.out_layout must be MIMO_LAYOUT_STREAM_MAJOR or _SYMBOL_MAJOR");
+  if (h->last_frames == 0) return fail(MIMO_ERR_STATE, "no batch has run on this handle");
+  if (h->det == MIMO_DET_SISO)
+    return fail(MIMO_ERR_UNSUPPORTED, "soft output with the SISO detector");
+  if (a->n_frames != h->last_frames || a->max_out_syms != h->last_max_out)
+    return fail(MIMO_ERR_ARG, "n_frames and max_out_syms must be the last batch's");
+  const uint64_t rows = (uint64_t)a->n_frames * h->N * a->max_out_syms;
+  if (rows >= 0xFFFFFFFFull) return fail(MIMO_ERR_ARG, "too many symbol rows");
+  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
+  int rc = launch_batch_mse(h, a->n_frames, s);
+  if (rc) return rc;
+  SoftArgs k{};
+  k.sym = reinterpret_cast<const float2 *>(a->d_sym);
+  k.llr = a->d_llr;
+  k.total = rows * h->M_occ;
+  k.rows = (uint32_t)rows;
+  k.N = h->N; k.M_occ = h->M_occ; k.max_out = a->max_out_syms;
+  k.symbol_major = a->out_layout == MIMO_LAYOUT_SYMBOL_MAJOR;
+  k.f32 = a->format == MIMO_LLR_F32;
+  k.bits = h->qam.b;
+  k.qam_scale = h->qam.scale;
+  k.llr_scale = a->llr_scale;
+  k.info = h->info.p;
+  k.nu = h->nu.p;
+  if (!launch_soft_demap(k, s)) return fail(MIMO_ERR_UNSUPPORTED, "no soft demapper for this QAM order");
+  HIPCHK(hipGetLastError());
+  return MIMO_OK;
+}
+
+int mimo_rx_batch_mse(mimo_rx *h, float *mse, uint32_t F) {
+  if (!h || !mse) return fail(MIMO_ERR_ARG, "null argument");
+  if (h->last_frames == 0) return fail(MIMO_ERR_STATE, "no batch has run on this handle");
+  if (h->det == MIMO_DET_SISO)
+    return fail(MIMO_ERR_UNSUPPORTED, "post-detection MSE with the SISO detector");
+  if (F > h->last_frames) return fail(MIMO_ERR_ARG, "more frames than the last batch");
+  if (F == 0) return MIMO_OK;
+  HIPCHK(hipDeviceSynchronize());
+  int rc = launch_batch_mse(h, h->last_frames, h->stream);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipMemcpy(mse, h->nu.p, sizeof(float) * (size_t)F * h->N * h->M_occ,
+                   hipMemcpyDeviceToHost));
   return MIMO_OK;
 }
 

@@ -334,6 +334,36 @@ struct EvmArgs {
 constexpr uint32_t kEvmChunks = 16;
 void launch_evm(const EvmArgs &a, uint32_t n_frames, hipStream_t s);
 
+// soft output (soft_kernels.hip): the post-detection MSE of a batch's frames and the max-log
+// LLRs of its equalised symbols; an opt-in pass after the decode (mimo_rx_soft_demap)
+struct MseArgs {
+  uint32_t N, M, M_occ;
+  const int32_t *occ_index;
+  const float2 *G;                 // [F][M][N][N]
+  const float2 *W;                 // [F][N(out)][N(rx)][M]
+  const float *gain;               // [F][M]
+  const FrameInfo *info;
+  float *nu;                       // [F][N][M_occ], zero rows for frames with status != 0
+};
+// false when N has no instance (nothing launched)
+bool launch_mse(const MseArgs &a, uint32_t n_frames, hipStream_t s);
+
+struct SoftArgs {
+  const float2 *sym;               // the batch's d_out_sym as total flat symbols
+  void *llr;                       // total groups of 2 bits int8 or float
+  uint64_t total;                  // rows M_occ
+  uint64_t mocc_recip;             // ceil(2^40 / M_occ) (set by launch_soft_demap)
+  uint32_t rows;                   // F N max_out
+  uint32_t N, M_occ, max_out;
+  int symbol_major;                // rows [F][max_out][N] instead of [F][N][max_out]
+  int f32;                         // MIMO_LLR_F32
+  uint32_t bits;                   // per dimension (1..4)
+  float qam_scale, llr_scale;
+  const FrameInfo *info;
+  const float *nu;
+};
+bool launch_soft_demap(SoftArgs a, hipStream_t s);
+
 // code tables: S0/S1 -> IFFT*dn (framing.cc:1054-1111, 1214-1262) -> zero-pad FFT_F
 struct CodesArgs {
   uint32_t M, N, nac, n_slots;

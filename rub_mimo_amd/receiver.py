@@ -268,6 +268,28 @@ class Receiver:
         check(lib().mimo_rx_batch_W(self._h, W.ctypes.data, n), "batch_W")
         return W
 
+    def soft_demap(self, out_sym, out_llr, n_frames=None, max_out=None, out_layout=0,
+                   fmt=_lib.LLR_I8, llr_scale=1.0, stream=None):
+        """Max-log LLRs of the last batch's equalised symbols (mimo_rx_soft_demap): out_sym is
+        that batch's out_sym (same out_layout and max_out), out_llr receives 2 log2(L) values
+        per symbol in the same row order, int8 (_lib.LLR_I8) or float32 (_lib.LLR_F32), scaled
+        by llr_scale / mse. Bit 0 is the demapped index's most significant bit; positive =
+        bit 0. Asynchronous on `stream`; rows the decode did not write get 0."""
+        a = _lib.SoftDemap(_ptr(out_sym), _ptr(out_llr),
+                           self._last if n_frames is None else n_frames,
+                           self.params.pid_max if max_out is None else max_out, out_layout, fmt,
+                           llr_scale)
+        check(lib().mimo_rx_soft_demap(self._h, C.byref(a), stream), "soft_demap")
+
+    def mse(self, n_frames=None):
+        """Post-detection mean-square error [n_frames][N][M_occ] of the last batch
+        (mimo_rx_batch_mse): the predicted E|y - s|^2 per frame slot, stream and occupied
+        carrier that scales the LLRs; zero rows for slots that did not sync."""
+        n = self._last if n_frames is None else n_frames
+        nu = np.zeros((n, self.params.num_streams, self.M_occ), np.float32)
+        check(lib().mimo_rx_batch_mse(self._h, nu.ctypes.data, n), "batch_mse")
+        return nu
+
     def set_siso(self, tx, rx):
         """framesync::set_siso_tx/rx: the stream pair the SISO detector decodes (a change
         invalidates the captured batch graph, whose kernels carry the indices)."""
