@@ -1472,10 +1472,12 @@ bool launch_search_ls(const SearchArgs &a, int log2F, int log2M, uint32_t n_fram
 // barriers of the transform order LDS only, so the prefetch stays in flight), transformed in
 // registers (the fused search's LS transform: RegPlan<LOG2M, 8> with the conflict-free
 // exchange layouts), multiplied by the S1 sign and summed in fp64 in code order. G and the
-// residual-variance partials are then ls_combine_q_kernel's bit for bit -- the same fp32 terms,
+// residual-variance partials equal ls_combine_q_kernel's to fp32 rounding -- the same terms,
 // summed in the same order, and the same reduction tree (64-lane butterfly, the four 64-runs of
-// each 256-subcarrier block left to right) -- without the terms' round trip through HBM
-// (268 MB each way per C3 x 64 batch).
+// each 256-subcarrier block left to right), but the two kernels' transforms contract into FMAs
+// differently, so the terms differ in their last bits
+// (test_ls_window_equals_fused_terms compares G to 2e-6, W and the sums to 1e-5) -- without the terms' round trip through
+// HBM (268 MB each way per C3 x 64 batch).
 //   With the opt-in CFO (CFO: a.cfo_part) the fused form's two corrections are one phasor
 // sequence on the window's samples: the folded form's stage-1 derotation (the search's
 // exp(-j 2 pi nu1 n) at window sample n - base) and the stage-2 residual's rotation of the code's
@@ -1645,9 +1647,15 @@ void ls_window_kernel(LsArgs a) {
   (void)NW;
 }
 
+// ls_window_kernel's limits: instances for 512 <= M <= 4096 (whole waves of M/8 threads; the
+// sign table LsArgs::s1sign_w exists for exactly these M), and with the opt-in CFO every code's
+// start phasor tabled in LDS
+bool ls_window_supported(int log2M, uint32_t nac, bool cfo) {
+  return log2M >= 9 && log2M <= 12 && (!cfo || nac <= (uint32_t)kLsRotCodes);
+}
+
 bool launch_ls_window(const LsArgs &a, int log2M, uint32_t n_frames, hipStream_t s) {
-  if (!a.s1sign_w || log2M < 9 || log2M > 12 || (a.cfo_part && a.nac > (uint32_t)kLsRotCodes))
-    return false;
+  if (!ls_window_supported(log2M, a.nac, a.cfo_part != nullptr) || !a.s1sign_w) return false;
   if (!n_frames) return true;
   void (*kern)(LsArgs) = nullptr;
   size_t shm = 0;

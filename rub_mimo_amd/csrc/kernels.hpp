@@ -208,9 +208,12 @@ constexpr uint32_t kLsCodesPerGroup = 4;   // access codes FFT'd per LS workgrou
 void launch_ls(const LsArgs &a, int log2M, uint32_t n_frames, hipStream_t s);
 void launch_ls_combine_q(const LsArgs &a, uint32_t n_frames, hipStream_t s);
 // the LS estimate straight from the access-code windows at the search's keys, no terms in HBM
-// (ls_window_kernel; 512 <= M <= 4096, CFO with nac <= 256): false when the geometry has no
-// instance
+// (ls_window_kernel): false, and nothing launched, unless ls_window_supported() and s1sign_w
+// is set
 bool launch_ls_window(const LsArgs &a, int log2M, uint32_t n_frames, hipStream_t s);
+// true when ls_window_kernel has an instance: 512 <= M <= 4096 (the M that get an s1sign_w
+// table), and under the opt-in CFO nac <= 256
+bool ls_window_supported(int log2M, uint32_t nac, bool cfo);
 
 // per-subcarrier weights, framing.cc:826-831 -> 1344-1367 (+ NxN ZF/MMSE)
 struct WeightArgs {

@@ -106,7 +106,7 @@ def test_chunked_execute_equals_one_shot(path):
 def test_batch_then_reset_then_chunked_execute_on_one_handle():
     """One handle runs a batch of 8 captures (its S&C records grow to F = 8 rows), then
     reset(), then the chunked streaming execute: the streaming path keeps only frame 0's
-    records across record growth (engine.cpp ensure_workspace), so its results still equal
+    records across record growth (engine_stages.cpp ensure_workspace), so its results still equal
     the golden fixture."""
     import ctypes as C
     g = load([p for p in GOLDEN if "m64_2x2_zf2" in p][0])
@@ -369,7 +369,7 @@ def test_set_siso_after_graph_capture_decodes_the_new_pair():
 
 
 def test_repeated_batch_graph_replay_is_identical():
-    """A repeated process() call is captured into a HIP graph and replayed (engine.cpp); its
+    """A repeated process() call is captured into a HIP graph and replayed (engine_batch.cpp); its
     results, symbols and indices must equal the direct launches bit for bit, and a changed
     argument must fall back to direct launches."""
     import torch
@@ -407,7 +407,7 @@ def test_repeated_batch_graph_replay_is_identical():
 
 def test_alternating_capture_buffers_replay_their_own_graphs():
     """Double-buffered ingest alternates two capture buffers: each batch key keeps its own
-    captured graph (a small cache in engine.cpp), and every replay equals the direct launch
+    captured graph (a small cache in engine_batch.cpp), and every replay equals the direct launch
     of the same buffer."""
     import torch
     M, cp, N, nac, pid, F = 256, 19, 4, 4, 24, 2
@@ -974,7 +974,7 @@ def test_two_phase_screen_finds_late_frames():
 
 
 def test_two_phase_screen_equals_one_pass():
-    """Early, late and frame-less captures in one batch: the two-phase S&C (engine.cpp
+    """Early, late and frame-less captures in one batch: the two-phase S&C (engine_stages.cpp
     run_sync) returns what one pass over every chunk returns (RMIMO_SC_PHASES=1, read once per
     process: a child interpreter), bit for bit, on every call -- direct launches, the captured
     graph and its replay. A capture without a frame reports zeros in the fields the estimation

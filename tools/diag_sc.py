@@ -1,7 +1,8 @@
 """tools/diag_sc.py -- per-stage timing and per-frame sync positions of the receive pipeline.
 
 Diagnostic only (GPU box): python tools/diag_sc.py [--frames F] [--reps R]
-Honours RMIMO_SC_BAND / RMIMO_DECODE_GRID (engine.cpp) for A/B runs.
+The library's RMIMO_* diagnostic switches (engine_diag.cpp: RMIMO_SC_PHASES, RMIMO_SC_COUNT,
+RMIMO_LS_FORM, ...) apply to the run as to any other.
 """
 import argparse
 import os
