@@ -253,6 +253,58 @@ int mimo_rx_soft_demap(mimo_rx *h, const mimo_soft_demap *a, void *hip_stream);
 /* host copy of nu, [n_frames][N][M_occ] floats; rows of unsynced slots are 0; synchronises */
 int mimo_rx_batch_mse(mimo_rx *h, float *mse, uint32_t n_frames);
 
+/* ---------------- ordered MMSE-SIC detection (absent from the reference: its detectors are
+ * linear) ----
+ * An opt-in pass after mimo_rx_process_batch over that batch's equalised symbols, like the soft
+ * output: the batch launches nothing for it, and the pass never modifies d_sym, the batch's
+ * d_out_idx, its results or the handle's G / W. It works with cfo_correct, with
+ * frames_per_capture > 1 and after MIMO_STAGES_DECODE.
+ *
+ * Per synced frame f and occupied carrier j (subcarrier k): G the frame's estimate [rx][tx], s2
+ * its noise_var (as mimo_rx_batch_results reports it), Q = G^H G, lambda = s2 for MIMO_DET_MMSE
+ * and 0 for MIMO_DET_ZF (and MIMO_DET_ZF2 at N = 2), R = Q + lambda I. The linear decode
+ * delivered y = g W X with g W = (Q + lambda I)^-1 G^H, so R y = G^H X: the matched-filter
+ * statistic comes back from y without the capture and without inverting W.
+ *
+ * N stages k = 0..N-1; S the undetected streams (all at k = 0), pi_0..pi_(k-1) the detected:
+ *   1. E = (Q[S,S] + s2 I)^-1, in fp64.
+ *   2. pi_k = the stream of S with the smallest real diagonal entry of E, ties to the lowest
+ *      stream index.
+ *   3. r = that row of E, beta = 1 - s2 E[pi_k][pi_k].
+ *   4. T[k][u] = (sum_{v in S} r_v R[v][u]) / beta, u = 0..N-1;
+ *      C[k][i] = (sum_{v in S} r_v Q[v][pi_i]) / beta, i < k   (fp64, stored as fp32).
+ *   5. nu_sic of stream pi_k = (1 - beta) / beta, the unbiased MMSE estimate's error power
+ *      (0 when s2 = 0).
+ *   6. per symbol: z_(pi_k) = sum_u T[k][u] y_u - sum_{i<k} C[k][i] s^_(pi_i); idx = the
+ *      decode's own slicer of z_(pi_k), s^_(pi_k) = the constellation point of idx.
+ * With MMSE, stage 0 is z = y_(pi_0) / beta_0, the unbiased linear output. A carrier whose fp64
+ * solve fails at any stage gets all-zero tables, order 0..N-1 and nu_sic 0 (as the linear
+ * path's W). Rows the decode does not write (frames with status != MIMO_FRAME_OK, symbols >=
+ * min(n_sym, max_out_syms)) get z = 0 and idx = 0: both outputs are fully defined after the
+ * call. A NaN in y gives a NaN z and whatever the slicer gives (level 0).
+ *
+ * MIMO_DET_SISO, and MIMO_DET_ZF2 at N != 2 (W is the identity there), return
+ * MIMO_ERR_UNSUPPORTED. */
+typedef struct mimo_sic_detect {
+  const void *d_sym;      /* the last batch's d_out_sym (same out_layout, max_out_syms) */
+  void *d_out_sym;        /* z, complex64, same shape and layout as d_sym, or NULL */
+  void *d_out_idx;        /* uint8 demapped index of z, same layout, or NULL (not both NULL) */
+  uint32_t n_frames;      /* frame slots, as mimo_rx_batch_results counts them */
+  uint32_t max_out_syms;
+  uint32_t out_layout;    /* MIMO_LAYOUT_* of the last batch */
+} mimo_sic_detect;
+/* Asynchronous on hip_stream (NULL: the handle's), no host synchronisation; the caller orders
+ * it after the batch that wrote d_sym. Allocates only when the slot count grows, so it can be
+ * captured into a graph after one warm-up call. Pointers 16-byte aligned; d_out_sym must not
+ * overlap d_sym; n_frames, max_out_syms and out_layout must equal the last batch's
+ * (MIMO_ERR_ARG); MIMO_ERR_STATE before any batch. */
+int mimo_rx_sic_detect(mimo_rx *h, const mimo_sic_detect *a, void *hip_stream);
+/* host copies of the last batch's detection order pi, [n_frames][M_occ][N] uint8, and of
+ * nu_sic, [n_frames][N][M_occ] floats indexed by stream; they work after any batch, with or
+ * without a detect call; rows of unsynced slots are 0; both synchronise */
+int mimo_rx_sic_order(mimo_rx *h, uint8_t *order, uint32_t n_frames);
+int mimo_rx_sic_mse(mimo_rx *h, float *mse, uint32_t n_frames);
+
 /* stage timing with HIP events on the handle's launch stream (for the roofline line).
  * stages: 0 S&C, 1 plateau, 2 search, 3 LS, 4 weights, 5 decode, 6 EVM reduce; an sc16 batch
  * that is widened internally (not read in place) adds its widening launch to stage 0 */

@@ -243,6 +243,7 @@ int mimo_rx_process_batch(mimo_rx *h, const mimo_batch *b, void *hip_stream) {
   if (rc) return rc;
   h->last_frames = b->n_frames * batch_fpc(b);
   h->last_max_out = b->max_out_syms;
+  h->last_layout = b->out_layout;
   return MIMO_OK;
 }
 

@@ -367,6 +367,37 @@ struct SoftArgs {
 };
 bool launch_soft_demap(SoftArgs a, hipStream_t s);
 
+// ordered MMSE-SIC detection (sic_kernels.hip): per-carrier tables from a batch's G and noise
+// variance, then one pass over its equalised symbols; opt-in, after the decode
+// (mimo_rx_sic_detect)
+constexpr uint32_t sic_c_rows(uint32_t N) { return N * (N - 1) / 2; }   // C[k][i], i < k
+struct SicTableArgs {
+  uint32_t N, M, M_occ;
+  int detector;                    // MIMO_DET_*: lambda = s2 for MMSE, else 0
+  const int32_t *occ_index;
+  const float2 *G;                 // [F][M][N][N]
+  const FrameInfo *info;
+  float2 *T;                       // [F][N(stage)][N(u)][M_occ]
+  float2 *C;                       // [F][sic_c_rows(N)][M_occ], row k (k - 1) / 2 + i
+  uint8_t *order;                  // [F][M_occ][N], zero rows for frames with status != 0
+  float *nu;                       // [F][N(stream)][M_occ], likewise
+};
+// false when N has no instance (nothing launched)
+bool launch_sic_tables(const SicTableArgs &a, uint32_t n_frames, hipStream_t s);
+
+struct SicApplyArgs {
+  const float2 *sym;               // the batch's d_out_sym
+  float2 *out_sym;                 // z, same layout, or null
+  uint8_t *out_idx;                // demapped index of z, same layout, or null
+  uint32_t N, M_occ, max_out;
+  int symbol_major;                // rows [F][max_out][N] instead of [F][N][max_out]
+  Qam qam;
+  const FrameInfo *info;
+  const float2 *T, *C;
+  const uint8_t *order;
+};
+bool launch_sic_apply(const SicApplyArgs &a, uint32_t n_frames, hipStream_t s);
+
 // code tables: S0/S1 -> IFFT*dn (framing.cc:1054-1111, 1214-1262) -> zero-pad FFT_F
 struct CodesArgs {
   uint32_t M, N, nac, n_slots;

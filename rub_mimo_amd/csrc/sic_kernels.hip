@@ -1,0 +1,401 @@
+// rub_mimo_amd/csrc/sic_kernels.hip -- ordered MMSE-SIC detection on gfx950: the per-carrier
+// detection order and tables of a batch's frames, and the pass that applies them to the batch's
+// equalised symbols (mimo_rx_sic_detect, DESIGN.md "SIC detection").
+//
+// No reference counterpart: framing.cc's detectors are linear. A separate, opt-in pass over the
+// decode's d_out_sym; nothing here is launched by the batch itself.
+//
+// Compiled with -ffp-contract=off: the slicer computes exactly floorf((z inv_scale + L) 0.5f),
+// which the tests restate bit for bit. The complex sums spell their fused multiply-adds out.
+// A frame slot is taken to hold fewer than 2^32 symbols (launch_sic_apply checks).
+#pragma clang fp contract(off)
+
+#include "fft.hpp"
+#include "kernels.hpp"
+
+namespace mimo {
+
+// ------------------------------------------------------------------------------------
+// Tables. One thread per (frame, subcarrier), everything in fp64: Q = G^H G, one Gauss-Jordan
+// solve with partial pivoting for E = (Q + s2 I)^-1, then N stages. Stage k picks the stream
+// pi of S with the smallest E[t][t], writes row k of T and C from row pi of E, and removes pi
+// from S without a new inversion: E_(S \ pi) = E[S',S'] - E[S',pi] E[pi,S'] / E[pi][pi].
+// Every array index is a loop counter (the row and column of pi are picked out by compares), so
+// for N <= 4 the loops unroll and Q and E live in registers. At N = 8 they stay loops and the
+// two 8x8 complex double matrices are runtime-indexed scratch (2 KiB per thread): accepted, the
+// kernel runs once per frame on N^2 M values and is not the hot path (DESIGN.md has the time).
+struct cdd { double re, im; };
+MIMO_DEV cdd cdd_mul(cdd a, cdd b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
+MIMO_DEV bool cdd_finite(cdd a) { return isfinite(a.re) && isfinite(a.im); }
+
+constexpr int kSicTabT = 64;
+template <int N>
+constexpr int sic_unroll() { return N <= 4 ? N : 1; }
+
+// Gauss-Jordan with partial pivoting on [A | B], as the weights' cd_solve; false on a zero pivot
+template <int N>
+MIMO_DEV bool sic_solve(cdd (&A)[N][N], cdd (&B)[N][N]) {
+  constexpr int U = sic_unroll<N>();
+#pragma unroll U
+  for (int c = 0; c < N; c++) {
+    int piv = c;
+    double best = -1.0;
+#pragma unroll U
+    for (int rr = 0; rr < N; rr++) {
+      const double m = A[rr][c].re * A[rr][c].re + A[rr][c].im * A[rr][c].im;
+      if (rr >= c && m > best) { best = m; piv = rr; }
+    }
+#pragma unroll U
+    for (int rr = 0; rr < N; rr++) {
+      if (rr > c && rr == piv) {
+#pragma unroll U
+        for (int k = 0; k < N; k++) {
+          const cdd t1 = A[c][k]; A[c][k] = A[rr][k]; A[rr][k] = t1;
+          const cdd t2 = B[c][k]; B[c][k] = B[rr][k]; B[rr][k] = t2;
+        }
+      }
+    }
+    const cdd d = A[c][c];
+    const double dd = d.re * d.re + d.im * d.im;
+    if (!(dd > 0.0)) return false;
+    const cdd inv = {d.re / dd, -d.im / dd};
+#pragma unroll U
+    for (int k = 0; k < N; k++) {
+      A[c][k] = cdd_mul(A[c][k], inv);
+      B[c][k] = cdd_mul(B[c][k], inv);
+    }
+#pragma unroll U
+    for (int rr = 0; rr < N; rr++) {
+      if (rr == c) continue;
+      const cdd fct = A[rr][c];
+#pragma unroll U
+      for (int k = 0; k < N; k++) {
+        const cdd x = cdd_mul(fct, A[c][k]), y = cdd_mul(fct, B[c][k]);
+        A[rr][k].re -= x.re; A[rr][k].im -= x.im;
+        B[rr][k].re -= y.re; B[rr][k].im -= y.im;
+      }
+    }
+  }
+  return true;
+}
+
+template <int N>
+__global__ __launch_bounds__(kSicTabT) void sic_tables_kernel(SicTableArgs a) {
+  constexpr int U = sic_unroll<N>();
+  constexpr int NC = (int)sic_c_rows(N);
+  const uint32_t f = blockIdx.y;
+  const uint32_t k = blockIdx.x * kSicTabT + threadIdx.x;
+  if (k >= a.M) return;
+  const int j = a.occ_index[k];
+  if (j < 0) return;
+  const uint64_t mo = a.M_occ;
+  float2 *Tq = a.T + (uint64_t)f * N * N * mo + j;        // [stage][u], stride M_occ
+  float2 *Cq = a.C + (uint64_t)f * NC * mo + j;           // [k (k - 1) / 2 + i]
+  uint8_t *oq = a.order + ((uint64_t)f * mo + j) * N;
+  float *nq = a.nu + (uint64_t)f * N * mo + j;            // [stream]
+  const FrameInfo &I = a.info[f];
+  bool fail = false;
+  if (I.status == 0) {
+    const double s2 = (double)I.noise_var;
+    const double lam = (a.detector == 2) ? s2 : 0.0;
+    const float2 *g = a.G + ((uint64_t)f * a.M + k) * N * N;
+    cdd Q[N][N], E[N][N];
+    {
+      cdd A[N][N];
+#pragma unroll U
+      for (int v = 0; v < N; v++)
+#pragma unroll U
+        for (int u = 0; u < N; u++) {
+          double sr = 0.0, si = 0.0;
+#pragma unroll U
+          for (int rr = 0; rr < N; rr++) {
+            const double gar = g[rr * N + v].x, gai = g[rr * N + v].y;
+            const double gbr = g[rr * N + u].x, gbi = g[rr * N + u].y;
+            sr += gar * gbr + gai * gbi;
+            si += gar * gbi - gai * gbr;
+          }
+          Q[v][u] = {sr, si};
+          A[v][u] = {sr + ((v == u) ? s2 : 0.0), si};
+          E[v][u] = {(v == u) ? 1.0 : 0.0, 0.0};
+        }
+      fail = !sic_solve<N>(A, E);
+    }
+    uint32_t active = (1u << N) - 1u;
+    int stage_of[N];
+#pragma unroll U
+    for (int t = 0; t < N; t++) stage_of[t] = 0;
+#pragma unroll U
+    for (int st = 0; st < N; st++) {
+      if (fail) break;
+      // the stream of S with the smallest real diagonal entry, the lowest index on a tie
+      int pi = -1;
+      double best = 0.0;
+#pragma unroll U
+      for (int t = 0; t < N; t++) {
+        const bool in = (active >> t) & 1u;
+        if (in && (pi < 0 || E[t][t].re < best)) { best = E[t][t].re; pi = t; }
+      }
+      // row and column pi of E
+      cdd row[N], col[N];
+#pragma unroll U
+      for (int t = 0; t < N; t++) {
+        row[t] = col[t] = {0.0, 0.0};
+#pragma unroll U
+        for (int v = 0; v < N; v++) {
+          if (v == pi) { row[t] = E[v][t]; col[t] = E[t][v]; }
+        }
+        if (!((active >> t) & 1u)) row[t] = col[t] = {0.0, 0.0};
+        if (!cdd_finite(row[t])) fail = true;
+      }
+      const double beta = 1.0 - s2 * best;
+      if (!(best > 0.0) || !(beta > 0.0)) fail = true;
+      if (fail) break;
+      const double ib = 1.0 / beta;
+#pragma unroll U
+      for (int u = 0; u < N; u++) {
+        cdd rq = {0.0, 0.0};          // sum_{v in S} r_v Q[v][u] (row is zero off S)
+#pragma unroll U
+        for (int v = 0; v < N; v++) {
+          const cdd p = cdd_mul(row[v], Q[v][u]);
+          rq.re += p.re; rq.im += p.im;
+        }
+        if (!((active >> u) & 1u))    // u = pi_i, i = stage_of[u] < st
+          Cq[(uint64_t)(st * (st - 1) / 2 + stage_of[u]) * mo] =
+              make_float2((float)(rq.re * ib), (float)(rq.im * ib));
+        Tq[(uint64_t)(st * N + u) * mo] = make_float2((float)((rq.re + lam * row[u].re) * ib),
+                                                      (float)((rq.im + lam * row[u].im) * ib));
+        if (u == pi) {
+          nq[(uint64_t)u * mo] = (float)(s2 * best * ib);
+          stage_of[u] = st;
+        }
+      }
+      oq[st] = (uint8_t)pi;
+      // E of S \ pi
+      const double id = 1.0 / best;
+#pragma unroll U
+      for (int r = 0; r < N; r++)
+#pragma unroll U
+        for (int c = 0; c < N; c++) {
+          const cdd p = cdd_mul(col[r], row[c]);
+          E[r][c].re -= p.re * id;
+          E[r][c].im -= p.im * id;
+        }
+      active &= ~(1u << pi);
+    }
+  }
+  if (I.status != 0 || fail) {
+    // an unsynced slot: all zero; a failed solve: zero tables, order 0..N-1, nu 0
+    const float2 z = make_float2(0.0f, 0.0f);
+    for (int e = 0; e < N * N; e++) Tq[(uint64_t)e * mo] = z;
+    for (int e = 0; e < NC; e++) Cq[(uint64_t)e * mo] = z;
+    for (int t = 0; t < N; t++) {
+      oq[t] = (I.status == 0) ? (uint8_t)t : (uint8_t)0;
+      nq[(uint64_t)t * mo] = 0.0f;
+    }
+  }
+}
+
+template <int N>
+static void sic_tables_launch(const SicTableArgs &a, uint32_t nf, hipStream_t s) {
+  hipLaunchKernelGGL((sic_tables_kernel<N>), dim3((a.M + kSicTabT - 1) / kSicTabT, nf),
+                     dim3(kSicTabT), 0, s, a);
+}
+
+bool launch_sic_tables(const SicTableArgs &a, uint32_t n_frames, hipStream_t s) {
+  if (n_frames == 0) return true;
+  if (n_frames > 65535u) return false;
+  switch (a.N) {
+    case 1: sic_tables_launch<1>(a, n_frames, s); return true;
+    case 2: sic_tables_launch<2>(a, n_frames, s); return true;
+    case 3: sic_tables_launch<3>(a, n_frames, s); return true;
+    case 4: sic_tables_launch<4>(a, n_frames, s); return true;
+    case 8: sic_tables_launch<8>(a, n_frames, s); return true;
+    default: return false;
+  }
+}
+
+// ------------------------------------------------------------------------------------
+// The symbol pass. A workgroup owns (frame, tile of kSicT adjacent carriers, kSicSB symbols);
+// thread tid holds carrier j's order and tables (N^2 + N (N - 1) / 2 complex values) in
+// registers for all of them. Per iteration it takes SC symbols: all SC N loads of y (8 bytes per
+// lane, a wave reads 512 contiguous bytes of a row) are issued before the first stage waits,
+// then per symbol the N stages run in order (packed fp32 fused multiply-adds, C held negated),
+// each one's z stored straight to the row of its stream (pi differs per lane, but changes
+// slowly along the carriers). z leaves as 8-byte stores. The indices do not leave as one byte
+// per lane (a byte store per lane costs a write transaction each, see soft_demap_kernel): every
+// thread puts its bytes into an LDS image [symbol][stream][carrier] of the iteration, and the
+// image leaves as dword stores, at most 3 single bytes at either end of a row whose address or
+// length is no multiple of 4. Loads and stores are non-temporal: every byte is touched once.
+constexpr int kSicT = 128;
+constexpr int kSicSB = 32;      // symbols per workgroup
+template <int N>
+constexpr int sic_sc() { return N <= 2 ? 8 : (N <= 4 ? 4 : 2); }   // symbols per iteration
+
+MIMO_DEV uint64_t sic_row(const SicApplyArgs &a, uint32_t f, uint32_t t, uint32_t s) {
+  return a.symbol_major ? ((uint64_t)f * a.max_out + s) * a.N + t
+                        : ((uint64_t)f * a.N + t) * a.max_out + s;
+}
+
+// acc += a b as two packed fused multiply-adds: (a.x, a.x) b + (a.y, a.y) (-b.y, b.x); br is
+// (-b.y, b.x)
+MIMO_DEV v2f sic_mac(v2f acc, float2 a, v2f b, v2f br) {
+  v2f ax, ay;
+  ax.x = ax.y = a.x;
+  ay.x = ay.y = a.y;
+  acc = __builtin_elementwise_fma(ax, b, acc);
+  return __builtin_elementwise_fma(ay, br, acc);
+}
+MIMO_DEV v2f sic_rot(v2f b) {
+  v2f r;
+  r.x = -b.y;
+  r.y = b.x;
+  return r;
+}
+
+// qam_demap and qam_point of its index in one go: the levels m of both dimensions give the
+// index (gray(mI) << b) | gray(mQ) and the point ((2 m - (L - 1)) scale), as qam_point finds
+// it from gray_dec of the index
+MIMO_DEV uint32_t sic_slice(v2f z, const Qam &q, v2f *point) {
+  const uint32_t mI = qam_level(z.x * q.inv_scale, q.L), mQ = qam_level(z.y * q.inv_scale, q.L);
+  point->x = (float)(int32_t)(2 * mI - (q.L - 1)) * q.scale;
+  point->y = (float)(int32_t)(2 * mQ - (q.L - 1)) * q.scale;
+  return (gray_enc(mI) << q.b) | gray_enc(mQ);
+}
+
+template <int N>
+__global__ __launch_bounds__(kSicT) void sic_apply_kernel(SicApplyArgs a) {
+  constexpr int SC = sic_sc<N>();
+  constexpr int NC = (int)sic_c_rows(N);
+  constexpr int SLOTS = kSicT / 4 + 1;   // dwords a row's kSicT bytes can touch
+  __shared__ __attribute__((aligned(16))) uint8_t img[SC * N * kSicT];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t f = blockIdx.z;
+  const uint32_t j0 = blockIdx.x * kSicT, j = j0 + tid;
+  const uint32_t s_lo = blockIdx.y * kSicSB;
+  const uint32_t s_hi = min(s_lo + (uint32_t)kSicSB, a.max_out);
+  const uint32_t nj = min((uint32_t)kSicT, a.M_occ - j0);
+  const bool lane = j < a.M_occ;
+  const FrameInfo &I = a.info[f];
+  const uint32_t n_out = (I.status == 0) ? min(I.n_sym, a.max_out) : 0u;
+  const uint64_t mo = a.M_occ;
+  // rows of one frame slot: stream t, symbol s at t r_ts + s r_ss
+  const uint32_t r_ts = a.symbol_major ? 1u : a.max_out, r_ss = a.symbol_major ? a.N : 1u;
+  const uint64_t fbase = (uint64_t)f * a.N * a.max_out * mo + j;   // (frame, carrier) in elements
+
+  float2 T[N][N], C[NC > 0 ? NC : 1];
+  uint32_t ord[N];       // stage k's stream as its element offset pi_k r_ts M_occ, and pi_k
+  uint32_t pis[N];
+  C[0] = make_float2(0.0f, 0.0f);
+  const bool work = lane && s_lo < n_out;
+#pragma unroll
+  for (int k = 0; k < N; k++) {
+    pis[k] = work ? min((uint32_t)a.order[((uint64_t)f * mo + j) * N + k], (uint32_t)(N - 1))
+                  : (uint32_t)k;
+    ord[k] = pis[k] * r_ts * a.M_occ;
+#pragma unroll
+    for (int u = 0; u < N; u++)
+      T[k][u] = work ? a.T[((uint64_t)f * N * N + k * N + u) * mo + j] : make_float2(0.0f, 0.0f);
+  }
+#pragma unroll
+  for (int e = 0; e < NC; e++)
+    C[e] = work ? cneg(a.C[((uint64_t)f * NC + e) * mo + j]) : make_float2(0.0f, 0.0f);
+
+  for (uint32_t s0 = s_lo; s0 < s_hi; s0 += SC) {
+    v2f y[SC][N];
+#pragma unroll
+    for (int q = 0; q < SC; q++)
+#pragma unroll
+      for (int u = 0; u < N; u++) y[q][u] = v2f{0.0f, 0.0f};
+    if (lane) {                         // one masked region for the loads, one for the stages
+#pragma unroll
+      for (int q = 0; q < SC; q++) {
+        if (s0 + q >= n_out) break;     // (uniform)
+#pragma unroll
+        for (int u = 0; u < N; u++)
+          y[q][u] = __builtin_nontemporal_load(reinterpret_cast<const v2f *>(
+              a.sym + fbase + ((uint64_t)u * r_ts + (uint64_t)(s0 + q) * r_ss) * mo));
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < SC; q++) {
+      const uint32_t s = s0 + q;
+      if (s >= s_hi || !lane) break;    // (s uniform; idle lanes' image bytes are never stored)
+      const uint64_t sbase = fbase + (uint64_t)s * r_ss * mo;
+      if (s < n_out) {                  // (uniform)
+        // stage k's z and index go straight to the row of its stream pi_k: the order changes
+        // slowly along the carriers, so a wave's store still covers whole runs of a row
+        v2f yr[N], sh[N], shr[N];
+#pragma unroll
+        for (int u = 0; u < N; u++) yr[u] = sic_rot(y[q][u]);
+#pragma unroll
+        for (int k = 0; k < N; k++) {
+          v2f z = v2f{0.0f, 0.0f};
+#pragma unroll
+          for (int u = 0; u < N; u++) z = sic_mac(z, T[k][u], y[q][u], yr[u]);
+#pragma unroll
+          for (int i = 0; i < k; i++) z = sic_mac(z, C[k * (k - 1) / 2 + i], sh[i], shr[i]);
+          const uint32_t idx = sic_slice(z, a.qam, &sh[k]);
+          shr[k] = sic_rot(sh[k]);
+          if (a.out_sym)
+            __builtin_nontemporal_store(z, reinterpret_cast<v2f *>(a.out_sym + sbase + ord[k]));
+          img[(q * N + pis[k]) * kSicT + tid] = (uint8_t)idx;
+        }
+      } else {                          // an erased row: z = 0, idx = 0
+#pragma unroll
+        for (int t = 0; t < N; t++) {
+          if (a.out_sym)
+            __builtin_nontemporal_store(v2f{0.0f, 0.0f}, reinterpret_cast<v2f *>(
+                a.out_sym + sbase + (uint64_t)t * r_ts * mo));
+          img[(q * N + t) * kSicT + tid] = 0;
+        }
+      }
+    }
+    if (a.out_idx) {                    // (uniform)
+      __syncthreads();
+      const uint32_t rows = min((uint32_t)SC, s_hi - s0) * N;
+      for (uint32_t w = tid; w < rows * SLOTS; w += kSicT) {
+        const uint32_t r = w / SLOTS, c = w - r * SLOTS;
+        const uint32_t q = r / N, t = r - q * N;
+        uint8_t *dst = a.out_idx + sic_row(a, f, t, s0 + q) * mo + j0;   // the row's nj bytes
+        const uint8_t *src = img + r * kSicT;
+        const uint32_t mis = (uint32_t)((uintptr_t)dst & 3u);
+        const int b0 = (int)(4 * c) - (int)mis;    // dword c of the aligned span: bytes b0..b0+3
+        if (b0 >= 0 && b0 + 4 <= (int)nj) {
+          uint32_t v;
+          if (mis == 0) v = *reinterpret_cast<const uint32_t *>(src + b0);
+          else v = (uint32_t)src[b0] | ((uint32_t)src[b0 + 1] << 8) |
+                   ((uint32_t)src[b0 + 2] << 16) | ((uint32_t)src[b0 + 3] << 24);
+          __builtin_nontemporal_store(v, reinterpret_cast<uint32_t *>(dst + b0));
+        } else {
+          for (int b = 0; b < 4; b++) {
+            const int bb = b0 + b;
+            if (bb >= 0 && bb < (int)nj) dst[bb] = src[bb];
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+template <int N>
+static void sic_apply_launch(const SicApplyArgs &a, uint32_t nf, hipStream_t s) {
+  const dim3 grid((a.M_occ + kSicT - 1) / kSicT, (a.max_out + kSicSB - 1) / kSicSB, nf);
+  hipLaunchKernelGGL((sic_apply_kernel<N>), grid, dim3(kSicT), 0, s, a);
+}
+
+bool launch_sic_apply(const SicApplyArgs &a, uint32_t n_frames, hipStream_t s) {
+  if (n_frames == 0 || a.max_out == 0 || a.M_occ == 0) return true;
+  if (n_frames > 65535u || (a.max_out + kSicSB - 1) / kSicSB > 65535u) return false;
+  if ((uint64_t)a.N * a.max_out * a.M_occ >= 0xFFFFFFFFull) return false;
+  switch (a.N) {
+    case 1: sic_apply_launch<1>(a, n_frames, s); return true;
+    case 2: sic_apply_launch<2>(a, n_frames, s); return true;
+    case 3: sic_apply_launch<3>(a, n_frames, s); return true;
+    case 4: sic_apply_launch<4>(a, n_frames, s); return true;
+    case 8: sic_apply_launch<8>(a, n_frames, s); return true;
+    default: return false;
+  }
+}
+
+}  // namespace mimo

@@ -290,6 +290,34 @@ class Receiver:
         check(lib().mimo_rx_batch_mse(self._h, nu.ctypes.data, n), "batch_mse")
         return nu
 
+    def sic_detect(self, sym, out_sym=None, out_idx=None, n_frames=None, max_out=None,
+                   out_layout=0, stream=None):
+        """Ordered MMSE-SIC detection of the last batch's equalised symbols
+        (mimo_rx_sic_detect): sym is that batch's out_sym (same out_layout and max_out); out_sym
+        receives the per-stage decision statistics z (complex64) and out_idx their demapped
+        indices (uint8), both in sym's shape and layout; either may be None, not both.
+        Asynchronous on `stream`; rows the decode did not write get 0."""
+        a = _lib.SicDetect(_ptr(sym), _ptr(out_sym), _ptr(out_idx),
+                           self._last if n_frames is None else n_frames,
+                           self.params.pid_max if max_out is None else max_out, out_layout)
+        check(lib().mimo_rx_sic_detect(self._h, C.byref(a), stream), "sic_detect")
+
+    def sic_order(self, n_frames=None):
+        """Detection order [n_frames][M_occ][N] (uint8 stream indices, first detected first) of
+        the last batch (mimo_rx_sic_order); zero rows for slots that did not sync."""
+        n = self._last if n_frames is None else n_frames
+        o = np.zeros((n, self.M_occ, self.params.num_streams), np.uint8)
+        check(lib().mimo_rx_sic_order(self._h, o.ctypes.data, n), "sic_order")
+        return o
+
+    def sic_mse(self, n_frames=None):
+        """Post-SIC mean-square error [n_frames][N][M_occ] by stream of the last batch
+        (mimo_rx_sic_mse): (1 - beta) / beta of the stage that detects the stream."""
+        n = self._last if n_frames is None else n_frames
+        nu = np.zeros((n, self.params.num_streams, self.M_occ), np.float32)
+        check(lib().mimo_rx_sic_mse(self._h, nu.ctypes.data, n), "sic_mse")
+        return nu
+
     def set_siso(self, tx, rx):
         """framesync::set_siso_tx/rx: the stream pair the SISO detector decodes (a change
         invalidates the captured batch graph, whose kernels carry the indices)."""
