@@ -305,6 +305,48 @@ int mimo_rx_sic_detect(mimo_rx *h, const mimo_sic_detect *a, void *hip_stream);
 int mimo_rx_sic_order(mimo_rx *h, uint8_t *order, uint32_t n_frames);
 int mimo_rx_sic_mse(mimo_rx *h, float *mse, uint32_t n_frames);
 
+/* ---------------- soft-output SIC: per-bit LLRs from the ordered MMSE-SIC pass ----
+ * One fused launch that runs the stages of mimo_rx_sic_detect and writes the max-log LLRs of
+ * every stage's z, weighted by that stage's nu_sic, without z going through memory. Opt-in and
+ * after the batch like the two passes it combines; the same conditions and side-effect rules as
+ * mimo_rx_sic_detect hold.
+ *
+ * The order, the tables T and C, z, idx and s^ are exactly steps 1-6 above; every stage still
+ * cancels its hard decision. For stream pi_k of a row the decode wrote, the 2b values are
+ *   LLR_i = llr_scale delta_i(z_(pi_k)) / max(nu_sic[f][pi_k][j], 1e-30)
+ * with delta_i the soft output's numerator: min over the levels with bit i = 1 minus min over
+ * the levels with bit i = 0 of (x - l_m)^2, bit i counted from the index's most significant
+ * bit, values 0..b-1 from x = Re z and b..2b-1 from x = Im z, the levels qam_point's fp32
+ * levels; positive = bit 0 more likely. z is unbiased, so nothing is unbiased again, and a
+ * non-zero LLR's sign is the matching bit of this call's idx. MIMO_LLR_F32 stores the fp32
+ * value, MIMO_LLR_I8 clamp(rintf(value), -127, 127) of that same fp32 value. A NaN z gives 0.
+ *
+ * d_llr is fully defined after the call. These get 0: rows the decode did not write (frames
+ * with status != MIMO_FRAME_OK, symbols >= min(n_sym, max_out_syms)), and every carrier whose
+ * fp64 solve failed (all-zero tables). The latter is not the good carrier with nu_sic = 0
+ * because s2 = 0: that one takes the 1e-30 floor.
+ *
+ * nu_sic is the error power of stage k's estimate when the earlier decisions were right
+ * (perfect cancellation): error propagation is not in the weight, so the LLRs of the later
+ * stages are optimistic where an earlier stage decided wrongly. */
+typedef struct mimo_sic_soft {
+  const void *d_sym;      /* the last batch's d_out_sym */
+  void *d_llr;            /* [d_sym's rows][M_occ][2b] int8 or float; required */
+  void *d_out_sym;        /* z, as mimo_sic_detect.d_out_sym, or NULL */
+  void *d_out_idx;        /* uint8 index of z, as mimo_sic_detect.d_out_idx, or NULL */
+  uint32_t n_frames, max_out_syms, out_layout;
+  uint32_t format;        /* MIMO_LLR_I8 / MIMO_LLR_F32 */
+  float llr_scale;        /* finite, > 0 */
+} mimo_sic_soft;
+/* Asynchronous on hip_stream (NULL: the handle's), no host synchronisation; the caller orders
+ * it after the batch that wrote d_sym. Allocates only when the slot count grows, so it can be
+ * captured into a graph after one warm-up call. Every pointer 16-byte aligned; d_out_sym must
+ * not overlap d_sym; n_frames, max_out_syms and out_layout must equal the last batch's; a bad
+ * format, out_layout or llr_scale and a null d_sym or d_llr are MIMO_ERR_ARG too;
+ * MIMO_ERR_STATE before any batch; MIMO_DET_SISO, and MIMO_DET_ZF2 at N != 2, return
+ * MIMO_ERR_UNSUPPORTED. */
+int mimo_rx_sic_soft(mimo_rx *h, const mimo_sic_soft *a, void *hip_stream);
+
 /* stage timing with HIP events on the handle's launch stream (for the roofline line).
  * stages: 0 S&C, 1 plateau, 2 search, 3 LS, 4 weights, 5 decode, 6 EVM reduce; an sc16 batch
  * that is widened internally (not read in place) adds its widening launch to stage 0 */

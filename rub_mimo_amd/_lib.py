@@ -62,6 +62,13 @@ class SicDetect(C.Structure):
                 ("out_layout", C.c_uint32)]
 
 
+class SicSoft(C.Structure):
+    _fields_ = [("d_sym", C.c_void_p), ("d_llr", C.c_void_p), ("d_out_sym", C.c_void_p),
+                ("d_out_idx", C.c_void_p), ("n_frames", C.c_uint32),
+                ("max_out_syms", C.c_uint32), ("out_layout", C.c_uint32),
+                ("format", C.c_uint32), ("llr_scale", C.c_float)]
+
+
 class FrameResult(C.Structure):
     _fields_ = [("status", C.c_int32), ("n_sym", C.c_uint32), ("trigger", C.c_uint64),
                 ("sync_index", C.c_uint64), ("num_samples_processed", C.c_uint64),
@@ -110,6 +117,7 @@ SIGNATURES = {
     "mimo_rx_soft_demap": (C.c_int, [_vp, _P(SoftDemap), _vp]),
     "mimo_rx_batch_mse": (C.c_int, [_vp, _vp, _u32]),
     "mimo_rx_sic_detect": (C.c_int, [_vp, _P(SicDetect), _vp]),
+    "mimo_rx_sic_soft": (C.c_int, [_vp, _P(SicSoft), _vp]),
     "mimo_rx_sic_order": (C.c_int, [_vp, _vp, _u32]),
     "mimo_rx_sic_mse": (C.c_int, [_vp, _vp, _u32]),
     "mimo_rx_set_timing": (C.c_int, [_vp, C.c_int]),

@@ -3,7 +3,7 @@
 //   engine.cpp         handles' life cycle, setters, plain getters, device/memcpy helpers
 //   engine_stages.cpp  workspace growth and the stage drivers (sync, estimate, decode)
 //   engine_batch.cpp   mimo_rx_process_batch: run_batch, the HIP-graph cache, batch getters
-//   engine_sic.cpp     mimo_rx_sic_detect and its getters: the SIC pass over the last batch
+//   engine_sic.cpp     mimo_rx_sic_detect, mimo_rx_sic_soft and the getters: the SIC passes
 //   engine_stream.cpp  mimo_rx_execute: the streaming framesync state machine, DEBUG_LOG
 //   engine_tx.cpp      transmitter, synthesiser, subcarrier-type and m-sequence helpers
 //   engine_diag.cpp    the RMIMO_* environment switches and the diagnostic reports
@@ -176,9 +176,10 @@ struct mimo_rx {
   DevBuf<float> nu;                          // soft output: post-detection MSE [F][N][M_occ]
   uint32_t last_layout = 0;                  // out_layout of the last batch
   // SIC detection (engine_sic.cpp): tables T [F][N][N][M_occ], C [F][N(N-1)/2][M_occ], the
-  // detection order [F][M_occ][N] and the post-SIC MSE [F][N][M_occ] of the last batch
+  // detection order [F][M_occ][N], the post-SIC MSE [F][N][M_occ] and the solved-carrier flags
+  // [F][M_occ] of the last batch
   DevBuf<float2> sic_T, sic_C;
-  DevBuf<uint8_t> sic_order;
+  DevBuf<uint8_t> sic_order, sic_ok;
   DevBuf<float> sic_nu;
   // streaming state (facade). The device capture holds samples [origin, origin + total) of
   // the stream since construction/reset (positions inside it are capture-relative).

@@ -302,6 +302,21 @@ class Receiver:
                            self.params.pid_max if max_out is None else max_out, out_layout)
         check(lib().mimo_rx_sic_detect(self._h, C.byref(a), stream), "sic_detect")
 
+    def sic_soft(self, sym, llr, out_sym=None, out_idx=None, n_frames=None, max_out=None,
+                 out_layout=0, fmt=_lib.LLR_I8, llr_scale=1.0, stream=None):
+        """Soft-output SIC of the last batch's equalised symbols (mimo_rx_sic_soft): the
+        stages of sic_detect, and into llr the max-log LLRs of every stage's z weighted by
+        llr_scale / nu_sic, 2 log2(L) values per symbol in sym's row order, int8
+        (_lib.LLR_I8) or float32 (_lib.LLR_F32). out_sym and out_idx optionally receive z and
+        its indices as sic_detect writes them. Bit 0 is the index's most significant bit;
+        positive = bit 0. Asynchronous on `stream`; rows the decode did not write and carriers
+        whose solve failed get 0."""
+        a = _lib.SicSoft(_ptr(sym), _ptr(llr), _ptr(out_sym), _ptr(out_idx),
+                         self._last if n_frames is None else n_frames,
+                         self.params.pid_max if max_out is None else max_out, out_layout, fmt,
+                         llr_scale)
+        check(lib().mimo_rx_sic_soft(self._h, C.byref(a), stream), "sic_soft")
+
     def sic_order(self, n_frames=None):
         """Detection order [n_frames][M_occ][N] (uint8 stream indices, first detected first) of
         the last batch (mimo_rx_sic_order); zero rows for slots that did not sync."""

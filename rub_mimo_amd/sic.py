@@ -13,12 +13,22 @@ S the undetected streams and pi_0..pi_(k-1) the detected ones:
   nu_sic[pi_k] = s2 E[pi_k][pi_k] / beta           (= (1 - beta) / beta)
   z_(pi_k) = sum_u T[k][u] y_u - sum_{i<k} C[k][i] s^_(pi_i);  s^_(pi_k) = slice(z_(pi_k))
 A carrier whose solve fails at any stage gets zero tables, order 0..N-1 and nu_sic 0.
+
+Soft output (mimo_rx_sic_soft): the same stages, every one still cancelling its hard decision,
+and per stage the max-log LLRs of its z,
+  LLR_i = llr_scale delta_i(z_(pi_k)) / max(nu_sic[pi_k], 1e-30)
+with delta_i the soft output's numerator (soft.llr_delta: min over the levels with bit i = 1
+minus min over the levels with bit i = 0, bit 0 the index's most significant bit, values
+0..b-1 from Re z and b..2b-1 from Im z, positive = bit 0). z is unbiased, so a non-zero LLR's
+sign is the matching bit of the stage's index. A NaN z gives 0, and so does every carrier whose
+solve failed: that is not the good carrier with nu_sic = 0 because s2 = 0, which takes the
+floor. nu_sic assumes perfect cancellation: error propagation is not in the weight.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from .soft import qam_bits, qam_levels
+from .soft import MSE_FLOOR, llr_delta, qam_bits, qam_levels
 
 
 def qam_inv_scale(qam_order):
@@ -182,3 +192,27 @@ def sic_apply(y, order, T, C, qam_order, decided=None, with_mag=False):
         use = ik if decided is None else np.asarray(decided)[pi, :, ar].T
         shat.append(qam_points(use, qam_order))
     return (z, idx, mag) if with_mag else (z, idx)
+
+
+def failed_carriers(T):
+    """The carriers whose solve failed, [J] bool, read off tables T [J][N][N] as sic_tables
+    returns them: a failed carrier's tables are all zero, and a good carrier's never are
+    (T[k][pi_k] is not 0)."""
+    T = np.asarray(T)
+    return ~np.any(T.reshape(T.shape[0], -1) != 0, axis=1)
+
+
+def sic_llr(z, nu_sic, qam_order, llr_scale=1.0, failed=None):
+    """Max-log LLRs [..., 2b] of the stage outputs z with their post-SIC error power nu_sic
+    (broadcast against z): llr_scale * soft.llr_delta(z) / max(nu_sic, 1e-30), float64.
+    Positive = bit 0; value i belongs to bit i of the stage's index counted from its most
+    significant bit. A NaN z gives 0; `failed` (bool, broadcast against z) marks the carriers
+    whose solve failed: they give 0, whereas a good carrier with nu_sic = 0 takes the floor."""
+    shape = np.shape(z)
+    nu = np.maximum(np.broadcast_to(np.asarray(nu_sic, np.float64), shape), MSE_FLOOR)
+    with np.errstate(invalid="ignore", over="ignore"):
+        out = llr_scale * llr_delta(z, qam_order) / nu[..., None]
+    out = np.where(np.isnan(out), 0.0, out)
+    if failed is not None:
+        out = np.where(np.broadcast_to(np.asarray(failed, bool), shape)[..., None], 0.0, out)
+    return out
