@@ -54,19 +54,37 @@ static int sic_pass_check(const mimo_rx *h, const void *d_sym, const void *d_out
   return MIMO_OK;
 }
 
-// the symbol pass's arguments over the tables launch_batch_sic_tables left in the handle
-static SicApplyArgs sic_apply_args(const mimo_rx *h, const void *d_sym, void *d_out_sym,
-                                   void *d_out_idx, uint32_t max_out_syms, uint32_t out_layout) {
-  SicApplyArgs k{};
-  k.sym = reinterpret_cast<const float2 *>(d_sym);
-  k.out_sym = reinterpret_cast<float2 *>(d_out_sym);
-  k.out_idx = reinterpret_cast<uint8_t *>(d_out_idx);
-  k.N = h->N; k.M_occ = h->M_occ; k.max_out = max_out_syms;
-  k.symbol_major = out_layout == MIMO_LAYOUT_SYMBOL_MAJOR;
+// both passes after their own argument checks: the shared checks, the tables, the symbol pass.
+// A null a->d_llr is the hard output (format and llr_scale are not looked at then).
+static int sic_pass(mimo_rx *h, const mimo_sic_soft *a, void *hip_stream) {
+  int rc = sic_pass_check(h, a->d_sym, a->d_out_sym, a->n_frames, a->max_out_syms, a->out_layout);
+  if (rc) return rc;
+  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
+  rc = launch_batch_sic_tables(h, a->n_frames, s);
+  if (rc) return rc;
+  SicPassArgs k{};
+  k.sym = reinterpret_cast<const float2 *>(a->d_sym);
+  k.out_sym = reinterpret_cast<float2 *>(a->d_out_sym);
+  k.out_idx = reinterpret_cast<uint8_t *>(a->d_out_idx);
+  k.N = h->N; k.M_occ = h->M_occ; k.max_out = a->max_out_syms;
+  k.symbol_major = a->out_layout == MIMO_LAYOUT_SYMBOL_MAJOR;
   k.qam = h->qam;
   k.info = h->info.p;
   k.T = h->sic_T.p; k.C = h->sic_C.p; k.order = h->sic_order.p;
-  return k;
+  if (a->d_llr) {
+    k.llr = a->d_llr;
+    k.nu = h->sic_nu.p;
+    k.ok = h->sic_ok.p;
+    k.llr_scale = a->llr_scale;
+    k.f32 = a->format == MIMO_LLR_F32;
+    k.bits = h->qam.b;
+  }
+  if (!launch_sic_pass(k, a->n_frames, s))
+    return fail(MIMO_ERR_UNSUPPORTED,
+                a->d_llr ? "no soft SIC kernel for this stream count, QAM order or batch shape"
+                         : "no SIC kernel for this stream count or batch shape");
+  HIPCHK(hipGetLastError());
+  return MIMO_OK;
 }
 
 extern "C" {
@@ -78,17 +96,10 @@ int mimo_rx_sic_detect(mimo_rx *h, const mimo_sic_detect *a, void *hip_stream) {
   if (((uintptr_t)a->d_sym & 15u) || ((uintptr_t)a->d_out_sym & 15u) ||
       ((uintptr_t)a->d_out_idx & 15u))
     return fail(MIMO_ERR_ARG, "d_sym, d_out_sym and d_out_idx must be 16-byte aligned");
-  int rc = sic_pass_check(h, a->d_sym, a->d_out_sym, a->n_frames, a->max_out_syms, a->out_layout);
-  if (rc) return rc;
-  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
-  rc = launch_batch_sic_tables(h, a->n_frames, s);
-  if (rc) return rc;
-  const SicApplyArgs k = sic_apply_args(h, a->d_sym, a->d_out_sym, a->d_out_idx, a->max_out_syms,
-                                        a->out_layout);
-  if (!launch_sic_apply(k, a->n_frames, s))
-    return fail(MIMO_ERR_UNSUPPORTED, "no SIC kernel for this stream count or batch shape");
-  HIPCHK(hipGetLastError());
-  return MIMO_OK;
+  mimo_sic_soft q{};     // d_llr null: hard output
+  q.d_sym = a->d_sym; q.d_out_sym = a->d_out_sym; q.d_out_idx = a->d_out_idx;
+  q.n_frames = a->n_frames; q.max_out_syms = a->max_out_syms; q.out_layout = a->out_layout;
+  return sic_pass(h, &q, hip_stream);
 }
 
 int mimo_rx_sic_soft(mimo_rx *h, const mimo_sic_soft *a, void *hip_stream) {
@@ -100,23 +111,7 @@ int mimo_rx_sic_soft(mimo_rx *h, const mimo_sic_soft *a, void *hip_stream) {
     return fail(MIMO_ERR_ARG, "llr_scale must be finite and positive");
   if (a->format != MIMO_LLR_I8 && a->format != MIMO_LLR_F32)
     return fail(MIMO_ERR_ARG, "mimo_sic_soft.format must be MIMO_LLR_I8 or _F32");
-  int rc = sic_pass_check(h, a->d_sym, a->d_out_sym, a->n_frames, a->max_out_syms, a->out_layout);
-  if (rc) return rc;
-  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
-  rc = launch_batch_sic_tables(h, a->n_frames, s);
-  if (rc) return rc;
-  SicSoftArgs k{};
-  k.s = sic_apply_args(h, a->d_sym, a->d_out_sym, a->d_out_idx, a->max_out_syms, a->out_layout);
-  k.llr = a->d_llr;
-  k.nu = h->sic_nu.p;
-  k.ok = h->sic_ok.p;
-  k.llr_scale = a->llr_scale;
-  k.f32 = a->format == MIMO_LLR_F32;
-  k.bits = h->qam.b;
-  if (!launch_sic_soft(k, a->n_frames, s))
-    return fail(MIMO_ERR_UNSUPPORTED, "no soft SIC kernel for this stream count, QAM order or batch shape");
-  HIPCHK(hipGetLastError());
-  return MIMO_OK;
+  return sic_pass(h, a, hip_stream);
 }
 
 // the getters' common part: the tables of every slot of the last batch, finished

@@ -382,12 +382,15 @@ struct SicTableArgs {
   uint8_t *order;                  // [F][M_occ][N], zero rows for frames with status != 0
   float *nu;                       // [F][N(stream)][M_occ], likewise
   uint8_t *ok;                     // [F][M_occ]: 1 where the frame synced and the carrier's
-                                   // solve succeeded (sic_soft_kernel's LLRs are 0 elsewhere)
+                                   // solve succeeded (sic_pass_kernel's LLRs are 0 elsewhere)
 };
 // false when N has no instance (nothing launched)
 bool launch_sic_tables(const SicTableArgs &a, uint32_t n_frames, hipStream_t s);
 
-struct SicApplyArgs {
+// the symbol pass: hard output (mimo_rx_sic_detect: llr null and bits 0; nu, ok, llr_scale and
+// f32 are not read) or the same pass with the max-log LLRs of every stage's z
+// (mimo_rx_sic_soft: out_sym and out_idx may both be null there)
+struct SicPassArgs {
   const float2 *sym;               // the batch's d_out_sym
   float2 *out_sym;                 // z, same layout, or null
   uint8_t *out_idx;                // demapped index of z, same layout, or null
@@ -397,22 +400,15 @@ struct SicApplyArgs {
   const FrameInfo *info;
   const float2 *T, *C;
   const uint8_t *order;
-};
-bool launch_sic_apply(const SicApplyArgs &a, uint32_t n_frames, hipStream_t s);
-
-// the same pass with the max-log LLRs of every stage's z (mimo_rx_sic_soft): s.out_sym and
-// s.out_idx may both be null here
-struct SicSoftArgs {
-  SicApplyArgs s;
-  void *llr;                       // [s.sym's rows][M_occ][2 bits] int8 or float
+  void *llr;                       // [sym's rows][M_occ][2 bits] int8 or float, or null
   const float *nu;                 // SicTableArgs::nu
   const uint8_t *ok;               // SicTableArgs::ok
   float llr_scale;
   int f32;                         // MIMO_LLR_F32
-  uint32_t bits;                   // per dimension (1..4)
+  uint32_t bits;                   // per dimension (1..4), 0 for hard output
 };
 // false when (N, bits) has no instance or the batch shape does not fit (nothing launched)
-bool launch_sic_soft(const SicSoftArgs &a, uint32_t n_frames, hipStream_t s);
+bool launch_sic_pass(const SicPassArgs &a, uint32_t n_frames, hipStream_t s);
 
 // code tables: S0/S1 -> IFFT*dn (framing.cc:1054-1111, 1214-1262) -> zero-pad FFT_F
 struct CodesArgs {

@@ -9,7 +9,7 @@
 // Compiled with -ffp-contract=off: the slicer computes exactly floorf((z inv_scale + L) 0.5f),
 // which the tests restate bit for bit. The complex sums spell their fused multiply-adds out.
 // Both LLR formats compute the same fp32 value for the same reason (llr.hpp).
-// A frame slot is taken to hold fewer than 2^32 symbols (launch_sic_apply checks).
+// A frame slot is taken to hold fewer than 2^32 symbols (launch_sic_pass checks).
 #pragma clang fp contract(off)
 
 #include <type_traits>
@@ -222,7 +222,9 @@ bool launch_sic_tables(const SicTableArgs &a, uint32_t n_frames, hipStream_t s) 
 }
 
 // ------------------------------------------------------------------------------------
-// The symbol pass. A workgroup owns (frame, tile of kSicT adjacent carriers, kSicSB symbols);
+// The symbol pass, one kernel for both outputs: sic_pass_kernel<N, B, F32>, B = 0 the hard
+// output (mimo_rx_sic_detect), B = 1..4 bits per dimension the soft output (mimo_rx_sic_soft).
+// A workgroup owns (frame, tile of kSicT adjacent carriers, kSicSB symbols);
 // thread tid holds carrier j's order and tables (N^2 + N (N - 1) / 2 complex values) in
 // registers for all of them. Per iteration it takes SC symbols: all SC N loads of y (8 bytes per
 // lane, a wave reads 512 contiguous bytes of a row) are issued before the first stage waits,
@@ -233,12 +235,34 @@ bool launch_sic_tables(const SicTableArgs &a, uint32_t n_frames, hipStream_t s) 
 // thread puts its bytes into an LDS image [symbol][stream][carrier] of the iteration, and the
 // image leaves as dword stores, at most 3 single bytes at either end of a row whose address or
 // length is no multiple of 4. Loads and stores are non-temporal: every byte is touched once.
+//
+// Soft output (B > 0) adds to that and changes none of it (one body: z and idx are the hard
+// pass's bit for bit): per stage the 2 B max-log LLRs of its z weighted by
+// llr_scale / max(nu_sic, 1e-30) of the stage's stream (N weights in registers). B = 0
+// compiles none of it: no read of nu, ok or llr, no LLR image, no barrier unless out_idx is set.
+// A lane's 2 B values at a 2 B-element lane stride are the store pattern that cost the soft
+// demapper 2.49 ms (int8) and 16.2 ms (fp32) before its LDS image, so they leave the same way:
+// every thread puts them into an LDS image [symbol][stream][carrier][2 B] of the iteration, at
+// the row of its own pi_k like the index image, and the image leaves as contiguous 16-byte
+// non-temporal stores per row. A row of d_llr starts at any multiple of its M_occ 2 B (4)
+// bytes: the image row holds the row's bytes behind its own misalignment (address mod 16), so a
+// 16-byte chunk of the image is a 16-byte aligned chunk of d_llr, and only the chunks at
+// either end of a row whose address or length is no multiple of 16 leave in narrower pieces.
+// The image sets the symbols per iteration: sic_sc<N>() halved until it fits kSicLlrImg.
+//
+// The four phases (table prologue, one symbol's stages, LLR drain, index drain) are marked in
+// the body, not split into functions. Each was tried as a MIMO_DEV function on a per-lane
+// struct, one at a time: the symbol phase changed occupancy or scratch of 10 of the 45
+// instances, the LLR drain of 4, the prologue of 1 (N = 8 64-QAM fp32, 12 -> 20 B of scratch);
+// the index drain alone kept all three figures but changed every instance's instruction
+// stream. Inline, on plain arrays, all 45 instances compile to the instruction streams of the
+// two kernels this one replaced, so their measured times stand.
 constexpr int kSicT = 128;
 constexpr int kSicSB = 32;      // symbols per workgroup
 template <int N>
 constexpr int sic_sc() { return N <= 2 ? 8 : (N <= 4 ? 4 : 2); }   // symbols per iteration
 
-MIMO_DEV uint64_t sic_row(const SicApplyArgs &a, uint32_t f, uint32_t t, uint32_t s) {
+MIMO_DEV uint64_t sic_row(const SicPassArgs &a, uint32_t f, uint32_t t, uint32_t s) {
   return a.symbol_major ? ((uint64_t)f * a.max_out + s) * a.N + t
                         : ((uint64_t)f * a.N + t) * a.max_out + s;
 }
@@ -269,155 +293,7 @@ MIMO_DEV uint32_t sic_slice(v2f z, const Qam &q, v2f *point) {
   return (gray_enc(mI) << q.b) | gray_enc(mQ);
 }
 
-template <int N>
-__global__ __launch_bounds__(kSicT) void sic_apply_kernel(SicApplyArgs a) {
-  constexpr int SC = sic_sc<N>();
-  constexpr int NC = (int)sic_c_rows(N);
-  constexpr int SLOTS = kSicT / 4 + 1;   // dwords a row's kSicT bytes can touch
-  __shared__ __attribute__((aligned(16))) uint8_t img[SC * N * kSicT];
-  const uint32_t tid = threadIdx.x;
-  const uint32_t f = blockIdx.z;
-  const uint32_t j0 = blockIdx.x * kSicT, j = j0 + tid;
-  const uint32_t s_lo = blockIdx.y * kSicSB;
-  const uint32_t s_hi = min(s_lo + (uint32_t)kSicSB, a.max_out);
-  const uint32_t nj = min((uint32_t)kSicT, a.M_occ - j0);
-  const bool lane = j < a.M_occ;
-  const FrameInfo &I = a.info[f];
-  const uint32_t n_out = (I.status == 0) ? min(I.n_sym, a.max_out) : 0u;
-  const uint64_t mo = a.M_occ;
-  // rows of one frame slot: stream t, symbol s at t r_ts + s r_ss
-  const uint32_t r_ts = a.symbol_major ? 1u : a.max_out, r_ss = a.symbol_major ? a.N : 1u;
-  const uint64_t fbase = (uint64_t)f * a.N * a.max_out * mo + j;   // (frame, carrier) in elements
-
-  float2 T[N][N], C[NC > 0 ? NC : 1];
-  uint32_t ord[N];       // stage k's stream as its element offset pi_k r_ts M_occ, and pi_k
-  uint32_t pis[N];
-  C[0] = make_float2(0.0f, 0.0f);
-  const bool work = lane && s_lo < n_out;
-#pragma unroll
-  for (int k = 0; k < N; k++) {
-    pis[k] = work ? min((uint32_t)a.order[((uint64_t)f * mo + j) * N + k], (uint32_t)(N - 1))
-                  : (uint32_t)k;
-    ord[k] = pis[k] * r_ts * a.M_occ;
-#pragma unroll
-    for (int u = 0; u < N; u++)
-      T[k][u] = work ? a.T[((uint64_t)f * N * N + k * N + u) * mo + j] : make_float2(0.0f, 0.0f);
-  }
-#pragma unroll
-  for (int e = 0; e < NC; e++)
-    C[e] = work ? cneg(a.C[((uint64_t)f * NC + e) * mo + j]) : make_float2(0.0f, 0.0f);
-
-  for (uint32_t s0 = s_lo; s0 < s_hi; s0 += SC) {
-    v2f y[SC][N];
-#pragma unroll
-    for (int q = 0; q < SC; q++)
-#pragma unroll
-      for (int u = 0; u < N; u++) y[q][u] = v2f{0.0f, 0.0f};
-    if (lane) {                         // one masked region for the loads, one for the stages
-#pragma unroll
-      for (int q = 0; q < SC; q++) {
-        if (s0 + q >= n_out) break;     // (uniform)
-#pragma unroll
-        for (int u = 0; u < N; u++)
-          y[q][u] = __builtin_nontemporal_load(reinterpret_cast<const v2f *>(
-              a.sym + fbase + ((uint64_t)u * r_ts + (uint64_t)(s0 + q) * r_ss) * mo));
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < SC; q++) {
-      const uint32_t s = s0 + q;
-      if (s >= s_hi || !lane) break;    // (s uniform; idle lanes' image bytes are never stored)
-      const uint64_t sbase = fbase + (uint64_t)s * r_ss * mo;
-      if (s < n_out) {                  // (uniform)
-        // stage k's z and index go straight to the row of its stream pi_k: the order changes
-        // slowly along the carriers, so a wave's store still covers whole runs of a row
-        v2f yr[N], sh[N], shr[N];
-#pragma unroll
-        for (int u = 0; u < N; u++) yr[u] = sic_rot(y[q][u]);
-#pragma unroll
-        for (int k = 0; k < N; k++) {
-          v2f z = v2f{0.0f, 0.0f};
-#pragma unroll
-          for (int u = 0; u < N; u++) z = sic_mac(z, T[k][u], y[q][u], yr[u]);
-#pragma unroll
-          for (int i = 0; i < k; i++) z = sic_mac(z, C[k * (k - 1) / 2 + i], sh[i], shr[i]);
-          const uint32_t idx = sic_slice(z, a.qam, &sh[k]);
-          shr[k] = sic_rot(sh[k]);
-          if (a.out_sym)
-            __builtin_nontemporal_store(z, reinterpret_cast<v2f *>(a.out_sym + sbase + ord[k]));
-          img[(q * N + pis[k]) * kSicT + tid] = (uint8_t)idx;
-        }
-      } else {                          // an erased row: z = 0, idx = 0
-#pragma unroll
-        for (int t = 0; t < N; t++) {
-          if (a.out_sym)
-            __builtin_nontemporal_store(v2f{0.0f, 0.0f}, reinterpret_cast<v2f *>(
-                a.out_sym + sbase + (uint64_t)t * r_ts * mo));
-          img[(q * N + t) * kSicT + tid] = 0;
-        }
-      }
-    }
-    if (a.out_idx) {                    // (uniform)
-      __syncthreads();
-      const uint32_t rows = min((uint32_t)SC, s_hi - s0) * N;
-      for (uint32_t w = tid; w < rows * SLOTS; w += kSicT) {
-        const uint32_t r = w / SLOTS, c = w - r * SLOTS;
-        const uint32_t q = r / N, t = r - q * N;
-        uint8_t *dst = a.out_idx + sic_row(a, f, t, s0 + q) * mo + j0;   // the row's nj bytes
-        const uint8_t *src = img + r * kSicT;
-        const uint32_t mis = (uint32_t)((uintptr_t)dst & 3u);
-        const int b0 = (int)(4 * c) - (int)mis;    // dword c of the aligned span: bytes b0..b0+3
-        if (b0 >= 0 && b0 + 4 <= (int)nj) {
-          uint32_t v;
-          if (mis == 0) v = *reinterpret_cast<const uint32_t *>(src + b0);
-          else v = (uint32_t)src[b0] | ((uint32_t)src[b0 + 1] << 8) |
-                   ((uint32_t)src[b0 + 2] << 16) | ((uint32_t)src[b0 + 3] << 24);
-          __builtin_nontemporal_store(v, reinterpret_cast<uint32_t *>(dst + b0));
-        } else {
-          for (int b = 0; b < 4; b++) {
-            const int bb = b0 + b;
-            if (bb >= 0 && bb < (int)nj) dst[bb] = src[bb];
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
-
-template <int N>
-static void sic_apply_launch(const SicApplyArgs &a, uint32_t nf, hipStream_t s) {
-  const dim3 grid((a.M_occ + kSicT - 1) / kSicT, (a.max_out + kSicSB - 1) / kSicSB, nf);
-  hipLaunchKernelGGL((sic_apply_kernel<N>), grid, dim3(kSicT), 0, s, a);
-}
-
-bool launch_sic_apply(const SicApplyArgs &a, uint32_t n_frames, hipStream_t s) {
-  if (n_frames == 0 || a.max_out == 0 || a.M_occ == 0) return true;
-  if (n_frames > 65535u || (a.max_out + kSicSB - 1) / kSicSB > 65535u) return false;
-  if ((uint64_t)a.N * a.max_out * a.M_occ >= 0xFFFFFFFFull) return false;
-  switch (a.N) {
-    case 1: sic_apply_launch<1>(a, n_frames, s); return true;
-    case 2: sic_apply_launch<2>(a, n_frames, s); return true;
-    case 3: sic_apply_launch<3>(a, n_frames, s); return true;
-    case 4: sic_apply_launch<4>(a, n_frames, s); return true;
-    case 8: sic_apply_launch<8>(a, n_frames, s); return true;
-    default: return false;
-  }
-}
-
-// ------------------------------------------------------------------------------------
-// The symbol pass with soft output: sic_apply_kernel's loads, stages and stores, operation for
-// operation (z and idx come out bit-identical), and per stage the 2 B max-log LLRs of its z
-// weighted by llr_scale / max(nu_sic, 1e-30) of the stage's stream (N weights in registers).
-// A lane's 2 B values at a 2 B-element lane stride are the store pattern that cost the soft
-// demapper 2.49 ms (int8) and 16.2 ms (fp32) before its LDS image, so they leave the same way:
-// every thread puts them into an LDS image [symbol][stream][carrier][2 B] of the iteration, at
-// the row of its own pi_k like the index image, and the image leaves as contiguous 16-byte
-// non-temporal stores per row. A row of d_llr starts at any multiple of its M_occ 2 B (4)
-// bytes: the image row holds the row's bytes behind its own misalignment (address mod 16), so a
-// 16-byte chunk of the image is a 16-byte aligned chunk of d_llr, and only the chunks at
-// either end of a row whose address or length is no multiple of 16 leave in narrower pieces.
-// The image sets the symbols per iteration: sic_sc<N>() halved until it fits kSicLlrImg.
+// the LLR image of the soft output
 constexpr int kSicLlrImg = 40 * 1024;   // 3 workgroups per CU beside the index image
 template <int B, bool F32>
 constexpr int sic_llr_bps() { return F32 ? 8 * B : 2 * B; }   // LLR bytes per symbol
@@ -450,8 +326,8 @@ MIMO_DEV void sic_llr_put(uint8_t *p, const float *v) {
 }
 
 template <int N, int B, bool F32>
-__global__ __launch_bounds__(kSicT) void sic_soft_kernel(SicSoftArgs g) {
-  constexpr int SC = sic_soft_sc<N, B, F32>();
+__global__ __launch_bounds__(kSicT) void sic_pass_kernel(SicPassArgs a) {
+  constexpr int SC = B > 0 ? sic_soft_sc<N, B, F32>() : sic_sc<N>();
   constexpr int NC = (int)sic_c_rows(N);
   constexpr int SLOTS = kSicT / 4 + 1;   // dwords a row's kSicT index bytes can touch
   constexpr int BPS = sic_llr_bps<B, F32>();
@@ -459,9 +335,9 @@ __global__ __launch_bounds__(kSicT) void sic_soft_kernel(SicSoftArgs g) {
   constexpr int CH = RS / 16;            // 16-byte chunks a row's LLR bytes can touch
   typedef uint32_t v4u __attribute__((ext_vector_type(4)));
   typedef typename std::conditional<F32, uint32_t, uint16_t>::type edge_t;   // a row end's pieces
+  // B = 0 never names limg, so it is not allocated: the hard pass's LDS is the index image
   __shared__ __attribute__((aligned(16))) uint8_t limg[SC * N * RS];
   __shared__ __attribute__((aligned(16))) uint8_t img[SC * N * kSicT];
-  const SicApplyArgs &a = g.s;
   const uint32_t tid = threadIdx.x;
   const uint32_t f = blockIdx.z;
   const uint32_t j0 = blockIdx.x * kSicT, j = j0 + tid;
@@ -472,26 +348,32 @@ __global__ __launch_bounds__(kSicT) void sic_soft_kernel(SicSoftArgs g) {
   const FrameInfo &I = a.info[f];
   const uint32_t n_out = (I.status == 0) ? min(I.n_sym, a.max_out) : 0u;
   const uint64_t mo = a.M_occ;
+  // rows of one frame slot: stream t, symbol s at t r_ts + s r_ss
   const uint32_t r_ts = a.symbol_major ? 1u : a.max_out, r_ss = a.symbol_major ? a.N : 1u;
   const uint64_t fbase = (uint64_t)f * a.N * a.max_out * mo + j;   // (frame, carrier) in elements
   // d_llr's address of (frame, tile) mod 2^32: its low 4 bits are all the image needs
-  const uint32_t lbase = (uint32_t)(uintptr_t)g.llr + (f * a.N * a.max_out * a.M_occ + j0) * BPS;
+  uint32_t lbase = 0;
+  if constexpr (B > 0)
+    lbase = (uint32_t)(uintptr_t)a.llr + (f * a.N * a.max_out * a.M_occ + j0) * BPS;
 
+  // ---- phase 1, the table prologue: a lane without work gets zero tables, order 0..N-1
   float2 T[N][N], C[NC > 0 ? NC : 1];
   uint32_t ord[N];       // stage k's stream as its element offset pi_k r_ts M_occ, and pi_k
   uint32_t pis[N];
-  float wk[N];           // stage k's weight llr_scale / max(nu_sic of pi_k, 1e-30)
+  float wk[N];           // B > 0: stage k's weight llr_scale / max(nu_sic of pi_k, 1e-30)
   C[0] = make_float2(0.0f, 0.0f);
   const bool work = lane && s_lo < n_out;
   // a failed solve (or an unsynced slot): NaN in place of z makes every LLR exactly 0
-  const bool good = work && g.ok[(uint64_t)f * mo + j] != 0;
+  bool good = false;
+  if constexpr (B > 0) good = work && a.ok[(uint64_t)f * mo + j] != 0;
   const float nanv = __builtin_nanf("");
 #pragma unroll
   for (int k = 0; k < N; k++) {
     pis[k] = work ? min((uint32_t)a.order[((uint64_t)f * mo + j) * N + k], (uint32_t)(N - 1))
                   : (uint32_t)k;
     ord[k] = pis[k] * r_ts * a.M_occ;
-    wk[k] = work ? g.llr_scale / fmaxf(g.nu[((uint64_t)f * N + pis[k]) * mo + j], 1e-30f) : 0.0f;
+    if constexpr (B > 0)
+      wk[k] = work ? a.llr_scale / fmaxf(a.nu[((uint64_t)f * N + pis[k]) * mo + j], 1e-30f) : 0.0f;
 #pragma unroll
     for (int u = 0; u < N; u++)
       T[k][u] = work ? a.T[((uint64_t)f * N * N + k * N + u) * mo + j] : make_float2(0.0f, 0.0f);
@@ -520,9 +402,12 @@ __global__ __launch_bounds__(kSicT) void sic_soft_kernel(SicSoftArgs g) {
     for (int q = 0; q < SC; q++) {
       const uint32_t s = s0 + q;
       if (s >= s_hi || !lane) break;    // (s uniform; idle lanes' image bytes are never stored)
+      // ---- phase 2, one symbol's stages (or an erased row)
       const uint64_t sbase = fbase + (uint64_t)s * r_ss * mo;
       const uint32_t lsym = lbase + s * r_ss * a.M_occ * BPS;   // the symbol's rows, mod 2^32
       if (s < n_out) {                  // (uniform)
+        // stage k's z and index go straight to the row of its stream pi_k: the order changes
+        // slowly along the carriers, so a wave's store still covers whole runs of a row
         v2f yr[N], sh[N], shr[N];
 #pragma unroll
         for (int u = 0; u < N; u++) yr[u] = sic_rot(y[q][u]);
@@ -538,14 +423,16 @@ __global__ __launch_bounds__(kSicT) void sic_soft_kernel(SicSoftArgs g) {
           if (a.out_sym)
             __builtin_nontemporal_store(z, reinterpret_cast<v2f *>(a.out_sym + sbase + ord[k]));
           img[(q * N + pis[k]) * kSicT + tid] = (uint8_t)idx;
-          float lv[2 * B];
-          llr_dim<B>(good ? z.x : nanv, a.qam.scale, wk[k], lv);
-          llr_dim<B>(good ? z.y : nanv, a.qam.scale, wk[k], lv + B);
-          sic_llr_put<B, F32>(limg + (q * N + pis[k]) * RS + ((lsym + ord[k] * BPS) & 15u) +
-                                  tid * BPS, lv);
+          if constexpr (B > 0) {
+            float lv[2 * B];
+            llr_dim<B>(good ? z.x : nanv, a.qam.scale, wk[k], lv);
+            llr_dim<B>(good ? z.y : nanv, a.qam.scale, wk[k], lv + B);
+            sic_llr_put<B, F32>(limg + (q * N + pis[k]) * RS + ((lsym + ord[k] * BPS) & 15u) +
+                                    tid * BPS, lv);
+          }
         }
       } else {                          // an erased row: z = 0, idx = 0, LLRs 0
-        float lv[2 * B];
+        float lv[B > 0 ? 2 * B : 1];
 #pragma unroll
         for (int i = 0; i < 2 * B; i++) lv[i] = 0.0f;
 #pragma unroll
@@ -554,31 +441,39 @@ __global__ __launch_bounds__(kSicT) void sic_soft_kernel(SicSoftArgs g) {
             __builtin_nontemporal_store(v2f{0.0f, 0.0f}, reinterpret_cast<v2f *>(
                 a.out_sym + sbase + (uint64_t)t * r_ts * mo));
           img[(q * N + t) * kSicT + tid] = 0;
-          sic_llr_put<B, F32>(limg + (q * N + t) * RS +
-                                  ((lsym + (uint32_t)t * r_ts * a.M_occ * BPS) & 15u) + tid * BPS, lv);
+          if constexpr (B > 0)
+            sic_llr_put<B, F32>(limg + (q * N + t) * RS +
+                                    ((lsym + (uint32_t)t * r_ts * a.M_occ * BPS) & 15u) + tid * BPS, lv);
         }
       }
     }
-    __syncthreads();
+    // hard output: no barrier unless out_idx is set, then one before and one after its drain;
+    // soft output: one before the LLR drain, one after the index drain
+    const bool drain = B > 0 || a.out_idx;   // (uniform)
+    if (drain) __syncthreads();
     const uint32_t rows = min((uint32_t)SC, s_hi - s0) * N;
-    const uint32_t nb = nj * BPS;       // a row's LLR bytes in this tile
-    for (uint32_t w = tid; w < rows * CH; w += kSicT) {
-      const uint32_t r = w / CH, c = w - r * CH;
-      const uint32_t q = r / N, t = r - q * N;
-      uint8_t *dst = reinterpret_cast<uint8_t *>(g.llr) + (sic_row(a, f, t, s0 + q) * mo + j0) * BPS;
-      const uint32_t mis = (uint32_t)((uintptr_t)dst & 15u);
-      const uint8_t *src = limg + r * RS;           // image byte mis is dst[0]
-      uint8_t *al = dst - mis;                      // the aligned span: image byte b is al[b]
-      const uint32_t b0 = 16 * c;
-      if (b0 >= mis && b0 + 16 <= mis + nb) {
-        const v4u v = *reinterpret_cast<const v4u *>(src + b0);
-        __builtin_nontemporal_store(v, reinterpret_cast<v4u *>(al + b0));
-      } else {
-        for (uint32_t bb = b0; bb < b0 + 16; bb += sizeof(edge_t))
-          if (bb >= mis && bb < mis + nb)
-            *reinterpret_cast<edge_t *>(al + bb) = *reinterpret_cast<const edge_t *>(src + bb);
+    // ---- phase 3, the LLR image to d_llr: 16-byte chunks, narrower pieces at a row's ends
+    if constexpr (B > 0) {
+      const uint32_t nb = nj * BPS;     // a row's LLR bytes in this tile
+      for (uint32_t w = tid; w < rows * CH; w += kSicT) {
+        const uint32_t r = w / CH, c = w - r * CH;
+        const uint32_t q = r / N, t = r - q * N;
+        uint8_t *dst = reinterpret_cast<uint8_t *>(a.llr) + (sic_row(a, f, t, s0 + q) * mo + j0) * BPS;
+        const uint32_t mis = (uint32_t)((uintptr_t)dst & 15u);
+        const uint8_t *src = limg + r * RS;           // image byte mis is dst[0]
+        uint8_t *al = dst - mis;                      // the aligned span: image byte b is al[b]
+        const uint32_t b0 = 16 * c;
+        if (b0 >= mis && b0 + 16 <= mis + nb) {
+          const v4u v = *reinterpret_cast<const v4u *>(src + b0);
+          __builtin_nontemporal_store(v, reinterpret_cast<v4u *>(al + b0));
+        } else {
+          for (uint32_t bb = b0; bb < b0 + 16; bb += sizeof(edge_t))
+            if (bb >= mis && bb < mis + nb)
+              *reinterpret_cast<edge_t *>(al + bb) = *reinterpret_cast<const edge_t *>(src + bb);
+        }
       }
     }
+    // ---- phase 4, the index image to out_idx: dwords, single bytes at a row's ends
     if (a.out_idx) {                    // (uniform)
       for (uint32_t w = tid; w < rows * SLOTS; w += kSicT) {
         const uint32_t r = w / SLOTS, c = w - r * SLOTS;
@@ -601,41 +496,43 @@ __global__ __launch_bounds__(kSicT) void sic_soft_kernel(SicSoftArgs g) {
         }
       }
     }
-    __syncthreads();
+    if (drain) __syncthreads();
   }
 }
 
 template <int N, int B, bool F32>
-static void sic_soft_launch(const SicSoftArgs &a, uint32_t nf, hipStream_t s) {
-  const dim3 grid((a.s.M_occ + kSicT - 1) / kSicT, (a.s.max_out + kSicSB - 1) / kSicSB, nf);
-  hipLaunchKernelGGL((sic_soft_kernel<N, B, F32>), grid, dim3(kSicT), 0, s, a);
+static void sic_pass_launch(const SicPassArgs &a, uint32_t nf, hipStream_t s) {
+  const dim3 grid((a.M_occ + kSicT - 1) / kSicT, (a.max_out + kSicSB - 1) / kSicSB, nf);
+  hipLaunchKernelGGL((sic_pass_kernel<N, B, F32>), grid, dim3(kSicT), 0, s, a);
 }
 
 template <int N>
-static bool sic_soft_bits(const SicSoftArgs &a, uint32_t nf, hipStream_t s) {
+static bool sic_pass_bits(const SicPassArgs &a, uint32_t nf, hipStream_t s) {
   switch (a.bits * 2 + (a.f32 ? 1 : 0)) {
-    case 2: sic_soft_launch<N, 1, false>(a, nf, s); return true;
-    case 3: sic_soft_launch<N, 1, true>(a, nf, s); return true;
-    case 4: sic_soft_launch<N, 2, false>(a, nf, s); return true;
-    case 5: sic_soft_launch<N, 2, true>(a, nf, s); return true;
-    case 6: sic_soft_launch<N, 3, false>(a, nf, s); return true;
-    case 7: sic_soft_launch<N, 3, true>(a, nf, s); return true;
-    case 8: sic_soft_launch<N, 4, false>(a, nf, s); return true;
-    case 9: sic_soft_launch<N, 4, true>(a, nf, s); return true;
+    case 0: sic_pass_launch<N, 0, false>(a, nf, s); return true;
+    case 2: sic_pass_launch<N, 1, false>(a, nf, s); return true;
+    case 3: sic_pass_launch<N, 1, true>(a, nf, s); return true;
+    case 4: sic_pass_launch<N, 2, false>(a, nf, s); return true;
+    case 5: sic_pass_launch<N, 2, true>(a, nf, s); return true;
+    case 6: sic_pass_launch<N, 3, false>(a, nf, s); return true;
+    case 7: sic_pass_launch<N, 3, true>(a, nf, s); return true;
+    case 8: sic_pass_launch<N, 4, false>(a, nf, s); return true;
+    case 9: sic_pass_launch<N, 4, true>(a, nf, s); return true;
     default: return false;
   }
 }
 
-bool launch_sic_soft(const SicSoftArgs &a, uint32_t n_frames, hipStream_t s) {
-  if (n_frames == 0 || a.s.max_out == 0 || a.s.M_occ == 0) return true;
-  if (n_frames > 65535u || (a.s.max_out + kSicSB - 1) / kSicSB > 65535u) return false;
-  if ((uint64_t)a.s.N * a.s.max_out * a.s.M_occ >= 0xFFFFFFFFull) return false;
-  switch (a.s.N) {
-    case 1: return sic_soft_bits<1>(a, n_frames, s);
-    case 2: return sic_soft_bits<2>(a, n_frames, s);
-    case 3: return sic_soft_bits<3>(a, n_frames, s);
-    case 4: return sic_soft_bits<4>(a, n_frames, s);
-    case 8: return sic_soft_bits<8>(a, n_frames, s);
+bool launch_sic_pass(const SicPassArgs &a, uint32_t n_frames, hipStream_t s) {
+  if ((a.llr == nullptr) != (a.bits == 0)) return false;
+  if (n_frames == 0 || a.max_out == 0 || a.M_occ == 0) return true;
+  if (n_frames > 65535u || (a.max_out + kSicSB - 1) / kSicSB > 65535u) return false;
+  if ((uint64_t)a.N * a.max_out * a.M_occ >= 0xFFFFFFFFull) return false;
+  switch (a.N) {
+    case 1: return sic_pass_bits<1>(a, n_frames, s);
+    case 2: return sic_pass_bits<2>(a, n_frames, s);
+    case 3: return sic_pass_bits<3>(a, n_frames, s);
+    case 4: return sic_pass_bits<4>(a, n_frames, s);
+    case 8: return sic_pass_bits<8>(a, n_frames, s);
     default: return false;
   }
 }

@@ -1,5 +1,6 @@
 """GPU tests of the ordered MMSE-SIC detector (mimo_rx_sic_detect, mimo_rx_sic_order,
-mimo_rx_sic_mse; sic_kernels.hip) against the written definition in rub_mimo_amd/sic.py,
+mimo_rx_sic_mse; sic_tables_kernel and sic_pass_kernel's hard-output instances, B = 0, in
+sic_kernels.hip) against the written definition in rub_mimo_amd/sic.py,
 evaluated in float64 on the GPU's own downloaded G, noise variance and equalised symbols.
 The geometries, seeds and 30 dB of test_gpu_soft.py (every kernel instantiation N = 2, 4, 8,
 both output layouts, a row length that is no multiple of 4, the streaming decode's geometry),
@@ -14,15 +15,14 @@ import os
 import numpy as np
 import pytest
 
+from postpass_support import (N_FRAMES, NOISE_FRAME, _case_params, _n_out, _res_bytes, _sctype,
+                              _synth_capture)
 from rub_mimo_amd import _lib, sic
-from rub_mimo_amd import framing as fr
-from rub_mimo_amd.receiver import Receiver, RxParams, Synthesizer, SynthParams
+from rub_mimo_amd.receiver import Receiver, RxParams
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "m[0-9]*.npz")))
-LAYOUTS = [_lib.LAYOUT_STREAM_MAJOR, _lib.LAYOUT_SYMBOL_MAJOR]
-LAYOUT_IDS = ["stream_major", "symbol_major"]
 
 # M, cp, N, nac, pid, qam, detector, sctype, synthesiser seed (one whose three frames all sync)
 CASES = {
@@ -34,8 +34,6 @@ CASES = {
     "qam64_mmse_stream": (2048, 152, 4, 20, 4, 64, _lib.DET_MMSE, None, 70),
     "qam16_zf_1x1": (64, 16, 1, 4, 10, 16, _lib.DET_ZF, None, 79),
 }
-N_FRAMES = 3
-NOISE_FRAME = 1
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -44,34 +42,9 @@ def need_gpu():
         pytest.fail("no HIP device visible: the gpu tests need an MI355X")
 
 
-def _sctype(M, kind):
-    if kind == "liquid":
-        return fr.ofdmframe_init_liquid_sctype(M)
-    if kind == "all":
-        return np.full(M, 2, np.uint8)
-    return None
-
-
 def _sic_rc(rx, sym, osym, oidx, n_frames, max_out, layout=0):
     a = _lib.SicDetect(sym, osym, oidx, n_frames, max_out, layout)
     return _lib.lib().mimo_rx_sic_detect(rx._h, C.byref(a), None)
-
-
-def _synth_capture(M, cp, N, nac, pid, qam, p, seed, noise_frame=NOISE_FRAME, tx=None):
-    """N_FRAMES synthetic captures at 30 dB on the device, one replaced by a noise-only
-    capture (no plateau: MIMO_FRAME_NO_SYNC)."""
-    S = Synthesizer(SynthParams(M=M, cp_len=cp, num_streams=N, num_access_codes=nac, pid=pid,
-                                qam_order=qam, seed=seed, snr_db=30.0, p=p))
-    L = max(S.frame_len(i) for i in range(N_FRAMES))
-    iq = _lib.DeviceBuffer(N_FRAMES * N * L * 8)
-    S.generate(iq, L, L, N_FRAMES, tx_idx=tx)
-    _lib.check(_lib.lib().mimo_stream_sync(None), "sync")
-    if noise_frame is not None:
-        host = iq.download(np.complex64, N_FRAMES * N * L).reshape(N_FRAMES, N, L)
-        rng = np.random.default_rng(seed)
-        host[noise_frame] = 0.01 * (rng.standard_normal((N, L)) + 1j * rng.standard_normal((N, L)))
-        iq.upload(host)
-    return iq, L
 
 
 def _garbage(zs, zi, nsym):
@@ -138,21 +111,7 @@ def run_case(name, layout):
                 mo=mo, mocc=mocc, N=N)
 
 
-def _n_out(r, mo):
-    return min(r["n_sym"], mo) if r["status"] == _lib.FRAME_OK else 0
-
-
-def _res_bytes(res):
-    return [tuple(v.tobytes() if isinstance(v, np.ndarray) else v for v in r.values())
-            for r in res]
-
-
-def _case_params(fn):
-    fn = pytest.mark.parametrize("layout", LAYOUTS, ids=LAYOUT_IDS)(fn)
-    return pytest.mark.parametrize("name", list(CASES))(fn)
-
-
-@_case_params
+@_case_params(CASES)
 def test_order_and_mse_match_the_model(name, layout):
     """sic_order() is the model's order for the GPU's own G() and noise_var on every carrier,
     except where the model's two candidate MSEs of the first differing stage agree to 1e-6
@@ -192,7 +151,7 @@ def test_order_and_mse_match_the_model(name, layout):
         assert np.all(nu_g > 0)
 
 
-@_case_params
+@_case_params(CASES)
 def test_symbols_match_the_model_teacher_forced(name, layout):
     """Every stage's z against the model's, computed from the GPU's y and the GPU's own earlier
     decisions: |z_gpu - z_model| <= 1e-5 (sum_u |T[k][u]| |y_u| + sum_i |C[k][i]| |s^_i|). The
@@ -215,7 +174,7 @@ def test_symbols_match_the_model_teacher_forced(name, layout):
     print("%s layout %d: worst |z_gpu - z_model| / magnitude sum = %.3g" % (name, layout, worst))
 
 
-@_case_params
+@_case_params(CASES)
 def test_indices_are_the_slicer_of_z_and_erasures_are_zero(name, layout):
     """On every row the decode wrote, d_out_idx is the float32 restatement of qam_demap of the
     GPU's own z, exactly; every other row (the noise frame, symbols >= min(n_sym, max_out)) is
@@ -234,7 +193,7 @@ def test_indices_are_the_slicer_of_z_and_erasures_are_zero(name, layout):
     assert erased > 0
 
 
-@_case_params
+@_case_params(CASES)
 def test_idx_only_output_and_repeatability(name, layout):
     """A call with d_out_sym NULL gives the same indices (and writes no z); a second full call
     repeats both outputs bitwise; d_sym, the batch's d_out_idx and results() are unchanged."""

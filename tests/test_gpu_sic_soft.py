@@ -1,5 +1,6 @@
-"""GPU tests of the soft-output SIC pass (mimo_rx_sic_soft; sic_soft_kernel in sic_kernels.hip)
-against mimo_rx_sic_detect on the same batch (z and idx bitwise) and against the written
+"""GPU tests of the soft-output SIC pass (mimo_rx_sic_soft; sic_pass_kernel's soft instances,
+B > 0, in sic_kernels.hip) against mimo_rx_sic_detect, the same kernel body at B = 0, on the
+same batch (z and idx bitwise) and against the written
 definition in rub_mimo_amd/sic.py (sic_llr), evaluated in float64 on the call's own z and the
 handle's nu_sic. test_gpu_sic.py's cases (every N with a receiver, every QAM order, both
 layouts, a guard-band allocation whose rows are no multiple of 16 bytes, the streaming
@@ -12,15 +13,14 @@ import os
 import numpy as np
 import pytest
 
+from postpass_support import (N_FRAMES, NOISE_FRAME, _case_params, _n_out, _res_bytes, _sctype,
+                              _synth_capture)
 from rub_mimo_amd import _lib, sic, soft
-from rub_mimo_amd import framing as fr
-from rub_mimo_amd.receiver import Receiver, RxParams, Synthesizer, SynthParams
+from rub_mimo_amd.receiver import Receiver, RxParams
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "m[0-9]*.npz")))
-LAYOUTS = [_lib.LAYOUT_STREAM_MAJOR, _lib.LAYOUT_SYMBOL_MAJOR]
-LAYOUT_IDS = ["stream_major", "symbol_major"]
 FORMATS = [_lib.LLR_F32, _lib.LLR_I8]
 SCALES = (1.0, 0.05)
 
@@ -38,8 +38,6 @@ CASES = {
     # iteration of 8) on rows of 2 M_occ bytes, no multiple of 16
     "qpsk_zf_guard_2blocks": (64, 16, 2, 4, 34, 4, _lib.DET_ZF, "liquid", 79),
 }
-N_FRAMES = 3
-NOISE_FRAME = 1
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -48,34 +46,9 @@ def need_gpu():
         pytest.fail("no HIP device visible: the gpu tests need an MI355X")
 
 
-def _sctype(M, kind):
-    if kind == "liquid":
-        return fr.ofdmframe_init_liquid_sctype(M)
-    if kind == "all":
-        return np.full(M, 2, np.uint8)
-    return None
-
-
 def _soft_rc(rx, sym, llr, osym, oidx, n_frames, max_out, layout=0, fmt=_lib.LLR_I8, scale=1.0):
     a = _lib.SicSoft(sym, llr, osym, oidx, n_frames, max_out, layout, fmt, scale)
     return _lib.lib().mimo_rx_sic_soft(rx._h, C.byref(a), None)
-
-
-def _synth_capture(M, cp, N, nac, pid, qam, p, seed, noise_frame=NOISE_FRAME, tx=None):
-    """N_FRAMES synthetic captures at 30 dB on the device, one replaced by a noise-only
-    capture (no plateau: MIMO_FRAME_NO_SYNC)."""
-    S = Synthesizer(SynthParams(M=M, cp_len=cp, num_streams=N, num_access_codes=nac, pid=pid,
-                                qam_order=qam, seed=seed, snr_db=30.0, p=p))
-    L = max(S.frame_len(i) for i in range(N_FRAMES))
-    iq = _lib.DeviceBuffer(N_FRAMES * N * L * 8)
-    S.generate(iq, L, L, N_FRAMES, tx_idx=tx)
-    _lib.check(_lib.lib().mimo_stream_sync(None), "sync")
-    if noise_frame is not None:
-        host = iq.download(np.complex64, N_FRAMES * N * L).reshape(N_FRAMES, N, L)
-        rng = np.random.default_rng(seed)
-        host[noise_frame] = 0.01 * (rng.standard_normal((N, L)) + 1j * rng.standard_normal((N, L)))
-        iq.upload(host)
-    return iq, L
 
 
 class _Out:
@@ -166,21 +139,7 @@ def run_case(name, layout):
                 qam=qam, mo=mo, mocc=mocc, N=N, nb=nb)
 
 
-def _n_out(r, mo):
-    return min(r["n_sym"], mo) if r["status"] == _lib.FRAME_OK else 0
-
-
-def _res_bytes(res):
-    return [tuple(v.tobytes() if isinstance(v, np.ndarray) else v for v in r.values())
-            for r in res]
-
-
-def _case_params(fn):
-    fn = pytest.mark.parametrize("layout", LAYOUTS, ids=LAYOUT_IDS)(fn)
-    return pytest.mark.parametrize("name", list(CASES))(fn)
-
-
-@_case_params
+@_case_params(CASES)
 def test_z_and_idx_are_bitwise_those_of_sic_detect(name, layout):
     c = run_case(name, layout)
     assert c["res"][NOISE_FRAME]["status"] != _lib.FRAME_OK
@@ -207,7 +166,7 @@ def _delta_check(z, llr, nu, qam):
     return worst
 
 
-@_case_params
+@_case_params(CASES)
 def test_fp32_llrs_match_the_definition(name, layout):
     """fp32 LLRs at llr_scale 1 against the definition on the call's own z and the handle's
     nu_sic. Per element |LLR nu_sic - delta_ref(z)| <= 1e-5 (A^2 + |delta_ref|), A = max(|x|,
@@ -227,7 +186,7 @@ def test_fp32_llrs_match_the_definition(name, layout):
     print("%s layout %d: worst |LLR nu_sic - ref| / (A^2 + |ref|) = %.3g" % (name, layout, worst))
 
 
-@_case_params
+@_case_params(CASES)
 def test_int8_is_the_quantised_fp32(name, layout):
     c = run_case(name, layout)
     allv = []
@@ -244,7 +203,7 @@ def test_int8_is_the_quantised_fp32(name, layout):
     assert not np.any(allv == -128)
 
 
-@_case_params
+@_case_params(CASES)
 def test_erasures_are_zero_over_the_garbage(name, layout):
     c = run_case(name, layout)
     erased = 0
@@ -260,7 +219,7 @@ def test_erasures_are_zero_over_the_garbage(name, layout):
     assert erased > 0 and _n_out(c["res"][NOISE_FRAME], c["mo"]) == 0
 
 
-@_case_params
+@_case_params(CASES)
 def test_sign_of_a_nonzero_llr_is_the_bit_of_the_calls_idx(name, layout):
     c = run_case(name, layout)
     nb = c["nb"]
@@ -275,7 +234,7 @@ def test_sign_of_a_nonzero_llr_is_the_bit_of_the_calls_idx(name, layout):
                 assert np.array_equal(v[nz] < 0, bit[nz] == 1), (f, key, i)
 
 
-@_case_params
+@_case_params(CASES)
 def test_llr_only_call_repeats_and_side_effects(name, layout):
     """With both optional outputs NULL the LLRs are the same and the other buffers keep their
     garbage; a repeat call is bitwise equal; d_sym, the batch's d_out_idx, results(),

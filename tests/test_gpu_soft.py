@@ -11,15 +11,15 @@ import os
 import numpy as np
 import pytest
 
+from postpass_support import (LAYOUTS, N_FRAMES, NOISE_FRAME, _n_out, _res_bytes, _sctype,
+                              _synth_capture)
 from rub_mimo_amd import _lib, soft
-from rub_mimo_amd import framing as fr
-from rub_mimo_amd.receiver import Receiver, RxParams, Synthesizer, SynthParams
+from rub_mimo_amd.receiver import Receiver, RxParams
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "m[0-9]*.npz")))
 GOLDEN = [g for g in GOLDEN if "_stream" not in os.path.basename(g)]
-LAYOUTS = [_lib.LAYOUT_STREAM_MAJOR, _lib.LAYOUT_SYMBOL_MAJOR]
 SCALES = (1.0, 0.05)
 
 # M, cp, N, nac, pid, qam, detector, sctype, synthesiser seed (one whose three frames all sync:
@@ -32,8 +32,6 @@ CASES = {
     "qpsk_zf_guard": (64, 16, 2, 4, 10, 4, _lib.DET_ZF, "liquid", 79),
     "qam64_mmse_stream": (2048, 152, 4, 20, 4, 64, _lib.DET_MMSE, None, 70),
 }
-N_FRAMES = 3
-NOISE_FRAME = 1
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -42,34 +40,9 @@ def need_gpu():
         pytest.fail("no HIP device visible: the gpu tests need an MI355X")
 
 
-def _sctype(M, kind):
-    if kind == "liquid":
-        return fr.ofdmframe_init_liquid_sctype(M)
-    if kind == "all":
-        return np.full(M, 2, np.uint8)
-    return None
-
-
 def _soft_rc(rx, sym, llr, n_frames, max_out, layout=0, fmt=_lib.LLR_I8, scale=1.0):
     a = _lib.SoftDemap(sym, llr, n_frames, max_out, layout, fmt, scale)
     return _lib.lib().mimo_rx_soft_demap(rx._h, C.byref(a), None)
-
-
-def _synth_capture(M, cp, N, nac, pid, qam, p, seed, noise_frame=NOISE_FRAME, tx=None):
-    """N_FRAMES synthetic captures at 30 dB on the device, one replaced by a noise-only
-    capture (no plateau: MIMO_FRAME_NO_SYNC)."""
-    S = Synthesizer(SynthParams(M=M, cp_len=cp, num_streams=N, num_access_codes=nac, pid=pid,
-                                qam_order=qam, seed=seed, snr_db=30.0, p=p))
-    L = max(S.frame_len(i) for i in range(N_FRAMES))
-    iq = _lib.DeviceBuffer(N_FRAMES * N * L * 8)
-    S.generate(iq, L, L, N_FRAMES, tx_idx=tx)
-    _lib.check(_lib.lib().mimo_stream_sync(None), "sync")
-    if noise_frame is not None:
-        host = iq.download(np.complex64, N_FRAMES * N * L).reshape(N_FRAMES, N, L)
-        rng = np.random.default_rng(seed)
-        host[noise_frame] = 0.01 * (rng.standard_normal((N, L)) + 1j * rng.standard_normal((N, L)))
-        iq.upload(host)
-    return iq, L
 
 
 @functools.lru_cache(maxsize=None)
@@ -118,15 +91,6 @@ def run_case(name, layout):
         i8 = {k: tr(v) for k, v in i8.items()}
     return dict(y=y, d=d, res=res, nu=nu, f32=f32, i8=i8, again=again, before=before,
                 after=after, qam=qam, mo=mo, mocc=mocc, N=N)
-
-
-def _n_out(r, mo):
-    return min(r["n_sym"], mo) if r["status"] == _lib.FRAME_OK else 0
-
-
-def _res_bytes(res):
-    return [tuple(v.tobytes() if isinstance(v, np.ndarray) else v for v in r.values())
-            for r in res]
 
 
 @pytest.mark.parametrize("layout", LAYOUTS, ids=["stream_major", "symbol_major"])
