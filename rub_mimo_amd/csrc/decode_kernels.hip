@@ -165,12 +165,13 @@ __global__ __launch_bounds__(T) void decode_kernel(DecodeArgs a) {
 }
 
 // Persistent form for configurations whose N antennas fit one LDS batch (C1-C3): a grid of
-// ~2 workgroups per CU walks the (frame, symbol) items; the next item's N x M input is
+// the workgroups resident on the chip walks the (frame, symbol) items; the next item's N x M
+// input is
 // loaded into registers (16-byte loads) while the current item is transformed, so HBM
 // reads overlap the FFT and the NxN apply. Each thread owns 4 consecutive subcarriers per
 // group, so weights, gains, equalised symbols and indices move as 16-byte / 4-byte vectors.
-template <int LOG2M, int NA, int T, bool SB, bool PF, int REF>
-__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(PF ? 1 : 2 * T / 256)))
+template <int LOG2M, int NA, int T, int REF>
+__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(1)))
 void decode_persistent_kernel(DecodeArgs a) {
   constexpr int M = 1 << LOG2M, PB = lds_padded_len(M);
   constexpr int NPAIR = M / 2;                 // complex pairs per antenna body
@@ -238,7 +239,7 @@ void decode_persistent_kernel(DecodeArgs a) {
   };
 
   uint32_t item = blockIdx.x;
-  if constexpr (PF) fetch(item);
+  fetch(item);
   for (; item < total; item += gridDim.x) {
     // an opaque copy of the thread index: LDS/global address arithmetic is recomputed per
     // item instead of being hoisted out of the loop into (spilled) registers
@@ -247,14 +248,13 @@ void decode_persistent_kernel(DecodeArgs a) {
     uint32_t f, s;
     locate(item, f, s);
     DEC_PROF(const long long t0 = clock64();)
-    if constexpr (!PF) fetch(item);   // two resident workgroups hide each other's loads
     __syncthreads();   // the previous item's LDS reads are done
 #pragma unroll
     for (int r = 0; r < NA; r++)
 #pragma unroll
       for (int u = 0; u < NIN; u++)   // samples 2i, 2i+1 are adjacent in the padded image
         *reinterpret_cast<float4 *>(lds + r * PB + lds_pad(2 * (tid + u * T))) = pre[r][u];
-    if constexpr (PF) fetch(item + gridDim.x);   // next item's input in flight meanwhile
+    fetch(item + gridDim.x);   // next item's input in flight meanwhile
     __syncthreads();
     DEC_PROF(const long long t1 = clock64();)
     fft_lds_twl<LOG2M, T, NA, false>(lds, tw_lds, tid);
@@ -366,7 +366,6 @@ void decode_persistent_kernel(DecodeArgs a) {
           op[1] = make_float4(y[2].x, y[2].y, y[3].x, y[3].y);
         }
         if (a.out_idx) *reinterpret_cast<uint32_t *>(a.out_idx + o) = packed;
-        if constexpr (SB) __builtin_amdgcn_sched_barrier(0);   // stream t+1's W loads after t
       }
     }
     DEC_PROF(const long long t3 = clock64();)
@@ -514,7 +513,7 @@ MIMO_DEV uint32_t qam_slice(float2 y, const Qam &q, float2 &pt) {
   return (gray_enc((uint32_t)fI) << q.b) | gray_enc((uint32_t)fQ);
 }
 
-template <int LOG2M, int NA, bool SISO, int EX = 0>
+template <int LOG2M, int NA, bool SISO>
 __global__ __launch_bounds__(1 << (LOG2M - 2))
 __attribute__((amdgpu_waves_per_eu(4)))
 void decode_reg_kernel(DecodeArgs a) {
@@ -528,7 +527,7 @@ void decode_reg_kernel(DecodeArgs a) {
   const FrameInfo &I = a.info[f];
   const uint32_t n_out = (I.status == 0) ? min(I.n_sym, a.max_out) : 0u;
   if (s >= n_out) return;                  // uniform per workgroup
-  const int64_t abs0 = I.base + (int64_t)I.i0 + (int64_t)((EX & 1) ? 0 : s) * a.SL + a.cp;
+  const int64_t abs0 = I.base + (int64_t)I.i0 + (int64_t)s * a.SL + a.cp;
   const bool inb = abs0 >= 0 && abs0 + M <= (int64_t)a.frame_len;
 
   // per-thread base twiddles of passes 1..NP-1: e^{-2 pi i k/(NS R)}, k = j mod NS
@@ -557,7 +556,7 @@ void decode_reg_kernel(DecodeArgs a) {
       }
       dft_small<8, false>(v);
     }
-    if constexpr (!(EX & 32)) reg_passes<LOG2M, 1>(lds, v, w1, tid);
+    reg_passes<LOG2M, 1>(lds, v, w1, tid);
 #pragma unroll
     for (int q = 0; q < 4; q++) {
       X[g0][q] = v[q] * a.dn;              // (:561) x dft_normalizer
@@ -621,8 +620,7 @@ void decode_reg_kernel(DecodeArgs a) {
         for (int tb = 0; tb < TB; tb++)
 #pragma unroll
           for (int r = 0; r < NA; r++)
-            if constexpr (EX & 64) w[tb][r] = v2f{gn[q] * (float)(tb + 1), (float)r * 1e-3f};
-            else w[tb][r] = reinterpret_cast<const v2f *>(Wf + ((uint64_t)(t0 + tb) * NA + r) * M)[(EX & 4) ? 0 : (EX & 8) ? (k & 255) : k];
+            w[tb][r] = reinterpret_cast<const v2f *>(Wf + ((uint64_t)(t0 + tb) * NA + r) * M)[k];
 #pragma unroll
         for (int tb = 0; tb < TB; tb++) {
           const int t = t0 + tb;
@@ -642,8 +640,7 @@ void decode_reg_kernel(DecodeArgs a) {
       if (jq[q] < 0) continue;
       const float2 ye = make_float2(y[t].x, y[t].y);
       float2 sp;
-      uint32_t d;
-      if constexpr (EX & 16) { sp = ye; d = 0; } else d = qam_slice(ye, a.qam, sp);
+      const uint32_t d = qam_slice(ye, a.qam, sp);
       dpk[t] |= d << (8 * q);
       uint32_t refi = refq[t];
       if (a.ref_mode == 0) refi = d;
@@ -666,7 +663,6 @@ void decode_reg_kernel(DecodeArgs a) {
 #pragma unroll
     for (int q = 0; q < 4; q++) {
       if (jq[q] < 0) continue;
-      if ((EX & 2) && X[t][q].x != 12345.0f) continue;
       if (a.out_sym) a.out_sym[ob + jq[q]] = make_float2(X[t][q].x, X[t][q].y);
       if (a.out_idx) a.out_idx[ob + jq[q]] = (uint8_t)(dpk[t] >> (8 * q));
     }
@@ -789,7 +785,7 @@ static uint32_t decode_launch_na(const DecodeArgs &a, uint32_t nf, hipStream_t s
       const size_t shm = sizeof(float2) * (lds_padded_len(M) * NA + M / 2);
       auto pick = [&](auto ref) {
         constexpr int R = decltype(ref)::value;
-        return decode_persistent_kernel<LOG2M, NA, TP, false, true, R>;
+        return decode_persistent_kernel<LOG2M, NA, TP, R>;
       };
       auto kern = a.ref_mode == 1 ? pick(std::integral_constant<int, 1>{})
                 : a.ref_mode == 2 ? pick(std::integral_constant<int, 2>{})

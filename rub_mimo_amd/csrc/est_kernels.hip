@@ -1538,11 +1538,6 @@ void ls_window_kernel(LsArgs a) {
     __syncthreads();
   }
   auto load_win = [&](uint32_t c, v2f *xw) {
-#ifdef LSW_ABL_NOLOAD   // timing ablation (tools/build_var.sh): no window loads
-#pragma unroll
-    for (int e = 0; e < 8; e++) xw[e] = v2f{(float)(e + c), (float)lt};
-    return;
-#endif
     const int64_t wb = I.base + (int64_t)key_index(kp[(uint64_t)c * N]);
     if (wb >= 0 && wb + M <= L) {                      // uniform: one row base
       const auto xr = xs.row((uint64_t)wb);
@@ -1596,11 +1591,7 @@ void ls_window_kernel(LsArgs a) {
       load_win(c + 1, xn);
       sn = load_sign(c + 1);
     }
-#ifdef LSW_ABL_NOPF   // timing ablation: the next code's loads complete before this transform
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
     if constexpr (CFO) derotate(c, xw);
-#ifndef LSW_ABL_NOFFT   // timing ablation: no transform
     reg_compute<LOG2M, 8, 0, false>(xw, wm);
     if constexpr (S2REG) {   // two images in turn, one barrier per exchange
       reg_rest_pp<LOG2M, 8, 1, false>(pa, pb, xw, wm, lt);
@@ -1612,7 +1603,6 @@ void ls_window_kernel(LsArgs a) {
     } else {
       reg_rest_lay<LOG2M, 8, 1, false, true>(buf, xw, wm, lt);
     }
-#endif
 #pragma unroll
     for (int e = 0; e < 8; e++) {
       // X / S1 (S1 = +-1: a product with the sign, exact; a null subcarrier's term is +0)

@@ -65,6 +65,11 @@ MIMO_DEV v2f cmac_pk(v2f y, v2f w, v2f x) {   // y + w * x, as fma(w.xx, x, y) t
       : "+v"(y) : "v"(w), "v"(x));
   return y;
 }
+MIMO_DEV uint32_t cvt_u32_sat(float x) {   // v_cvt_u32_f32: NaN and negatives -> 0, saturating
+  uint32_t r;
+  asm("v_cvt_u32_f32 %0, %1" : "=v"(r) : "v"(x));
+  return r;
+}
 MIMO_DEV v2f add_mi(v2f a, v2f b) {      // a + b * (-i) = (a.x + b.y, a.y - b.x)
   v2f r;
   asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));

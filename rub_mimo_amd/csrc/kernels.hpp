@@ -109,8 +109,6 @@ struct FillArgs {
 void launch_fill(const FillArgs &a, hipStream_t s);
 // true when the geometry allows the screen (M/2 a multiple of kScrB, M <= 8192)
 inline bool sc_screen_ok(uint32_t M) { return M / 2 >= (uint32_t)kScrB && (M / 2) % kScrB == 0 && M / 2 / kScrB <= (uint32_t)kScrMaxD; }
-// copies one device word (the hot-item count after a screen phase)
-void launch_sc_snapshot(uint32_t *dst, const uint32_t *src, hipStream_t s);
 void launch_sc_screen(const ScreenArgs &a, uint32_t n_frames, hipStream_t s);
 void launch_sc_exact(const ScArgs &a, hipStream_t s);
 // persistent grid of n_cu x (resident blocks per CU) over the F x chunks items
@@ -310,7 +308,7 @@ bool decode_stream_accepts(const DecodeArgs &a, int log2M, uint32_t n_frames);
 // true when launch_decode_stream runs its CPE variant for these arguments (folded CFO
 // derotation and the per-symbol common phase)
 bool decode_stream_cpe(const DecodeArgs &a);
-// decode_stream.hip: 8x8 split form (spectra to a scratch, then a chunked apply, optionally
+// decode_split.hip: 8x8 split form (spectra to a scratch, then a chunked apply, optionally
 // alternating over symbol groups); 0 when the configuration is not handled or a.spec is null.
 // The scratch holds split_group_symbols(max_out) symbols per frame.
 uint32_t launch_decode_split(const DecodeArgs &a, int log2M, uint32_t n_frames, hipStream_t s);
@@ -321,6 +319,7 @@ uint32_t split_group_symbols(uint32_t max_out);
 // the split decode's symbol groups, symbol ranges per (group, chunk) and EVM records per frame
 uint32_t split_plan(uint32_t max_out, int log2M, uint32_t *groups, uint32_t *P);
 constexpr uint32_t kMaxEvmParts = 16;
+constexpr uint32_t kStreamMaxQam = 256;   // constellation points the LDS tables hold (256-QAM)
 
 struct EvmArgs {
   uint32_t N, max_out;

@@ -2076,12 +2076,6 @@ void launch_fill(const FillArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(fill_kernel, dim3(grid), dim3(256), 0, s, a);
 }
 
-__global__ void sc_snapshot_kernel(uint32_t *dst, const uint32_t *src) { *dst = *src; }
-
-void launch_sc_snapshot(uint32_t *dst, const uint32_t *src, hipStream_t s) {
-  hipLaunchKernelGGL(sc_snapshot_kernel, dim3(1), dim3(1), 0, s, dst, src);
-}
-
 void launch_sc_screen(const ScreenArgs &a, uint32_t n_frames, hipStream_t s) {
   const uint64_t end = a.chunk_hi ? std::min<uint64_t>(a.frame_len, a.chunk_hi * a.chunk_len)
                                   : (uint64_t)a.frame_len;

@@ -825,7 +825,7 @@ def test_c4_8x8_mmse_4096_256qam_reduced_codes():
 def test_c4_split_decode_matches_oracle():
     """The production C4 decode: with max_out >= M/64 the 8x8 frame takes the split form
     (spectra_persist_kernel<12> writes every symbol's spectra, apply_split2_kernel<8> applies
-    W, demaps and sums EVM; decode_stream.hip). PID 66 against the brute-force oracle with 2
+    W, demaps and sums EVM; decode_split.hip). PID 66 against the brute-force oracle with 2
     access codes: symbols within the EVM tolerance, indices, errors and EVM-dB."""
     _c_frame_parity(4096, 304, 8, 2, 66, 256, _lib.DET_MMSE, 35.0, seed=48, bias=False,
                     path=_lib.DECODE_SPLIT, out_idx=True)

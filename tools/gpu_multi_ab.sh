@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B/C.. of library builds on one box, alternating: LIBS = paths relative to the repo root
 # (the in-tree library is rub_mimo_amd/librub_mimo_amd.so), WL the workloads, REPS rounds;
-# PROF_LIBS = DS_PROF builds run once each with RMIMO_DEC_PROF=1 (cycle split on stderr)
+# PROF_LIBS = profile builds (make PROFILE=1) run once each with RMIMO_DEC_PROF=1 (cycle split on stderr)
 set -o pipefail
 O=gpurun_out/${TAG:-mab}
 mkdir -p $O

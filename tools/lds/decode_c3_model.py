@@ -1,5 +1,7 @@
 """Bank-conflict census of decode_stream_kernel<11,4> (C3) LDS accesses per symbol (one wave of
-each kind), using tools/lds/bank_model.py. Mirrors the kernel's address arithmetic."""
+each kind), using tools/lds/bank_model.py. Mirrors the address arithmetic of the kernel's
+earlier form, one region-wide padding (pad2 below) for the wave-local sub-transforms; the
+kernel in decode_stream.hip now has a layout per exchange, which decode_c3_x256.py counts."""
 import sys
 sys.path.insert(0, __file__.rsplit("/", 1)[0])
 from bank_model import cycles

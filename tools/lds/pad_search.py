@@ -53,4 +53,4 @@ for sh, msk in itertools.product(range(3, 8), [1, 3, 7, 15, 31]):
 cands.sort()
 for c in cands[:12]:
     print(c)
-print("pad2 (current):", score(lambda i: i + (i >> 5) + 4 * (i >> 6)))
+print("pad2 (the earlier region-wide padding):", score(lambda i: i + (i >> 5) + 4 * (i >> 6)))
