@@ -111,7 +111,7 @@ int build_codes(Codes &c, uint32_t M, uint32_t N, uint32_t nac, const uint8_t *p
 int copy_W(mimo_rx *h, uint32_t f, float *W) {
   const size_t n = (size_t)h->M * h->N * h->N;
   std::vector<float2> tmp(n);
-  HIPCHK(hipMemcpy(tmp.data(), h->W.p + (size_t)f * n, sizeof(float2) * n,
+  HIPCHK(hipMemcpy(tmp.data(), h->ws.W.p + (size_t)f * n, sizeof(float2) * n,
                    hipMemcpyDeviceToHost));
   float2 *o = reinterpret_cast<float2 *>(W);
   for (uint32_t t = 0; t < h->N; t++)
@@ -123,7 +123,7 @@ int copy_W(mimo_rx *h, uint32_t f, float *W) {
 
 int copy_corr(mimo_rx *h, uint32_t F, uint32_t *corr, uint32_t *s0) {
   std::vector<unsigned long long> k((size_t)F * h->N * h->n_slots);
-  HIPCHK(hipMemcpy(k.data(), h->keys.p, sizeof(unsigned long long) * k.size(),
+  HIPCHK(hipMemcpy(k.data(), h->ws.keys.p, sizeof(unsigned long long) * k.size(),
                    hipMemcpyDeviceToHost));
   auto idx = [](unsigned long long v) -> uint32_t {
     return v ? (0xFFFFFFFFu - (uint32_t)(v & 0xFFFFFFFFull)) : 0u;
@@ -400,7 +400,7 @@ int mimo_rx_get_G(mimo_rx *h, float *G) {
         for (uint32_t r = 0; r < h->N; r++) G[2 * ((k * h->N + r) * h->N + r)] = 1.0f;
     return MIMO_OK;
   }
-  HIPCHK(hipMemcpy(G, h->G.p, sizeof(float2) * n, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(G, h->ws.G.p, sizeof(float2) * n, hipMemcpyDeviceToHost));
   return MIMO_OK;
 }
 
@@ -417,7 +417,7 @@ int mimo_rx_get_gain(mimo_rx *h, float *gain) {
     return MIMO_OK;
   }
   std::vector<float> tmp(h->M);
-  HIPCHK(hipMemcpy(tmp.data(), h->gain.p, sizeof(float) * h->M, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(tmp.data(), h->ws.gain.p, sizeof(float) * h->M, hipMemcpyDeviceToHost));
   for (uint32_t k = 0; k < h->M; k++)
     if (h->occ_index[k] >= 0) gain[h->occ_index[k]] = tmp[k];
   return MIMO_OK;
@@ -461,12 +461,12 @@ int mimo_rx_get_cfo_mode(const mimo_rx *h, int32_t *mode) {
 int mimo_rx_get_sc_exact_count(mimo_rx *h, uint64_t *out) {
   if (!h || !out) return fail(MIMO_ERR_ARG, "null argument");
   *out = 0;
-  if (!h->n_exact.p) return MIMO_OK;
+  if (!h->ws.n_exact.p) return MIMO_OK;
   unsigned long long v = 0;
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(&v, h->n_exact.p, sizeof(v), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemset(h->n_exact.p, 0, sizeof(v)));
+  HIPCHK(hipMemcpy(&v, h->ws.n_exact.p, sizeof(v), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemset(h->ws.n_exact.p, 0, sizeof(v)));
   *out = v;
   return MIMO_OK;
 }

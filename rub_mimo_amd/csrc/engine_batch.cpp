@@ -47,14 +47,14 @@ static bool cfo_folds(const mimo_rx *h, const mimo_batch *b, bool widened) {
 }
 
 // opt-in CFO stage 1 over capture c: the coarse estimate per synced frame at its trigger into
-// h->cfo_eps (allocated by the caller), nothing derotated (out null, fold 0) until the caller
+// h->ws.cfo_eps (allocated by the caller), nothing derotated (out null, fold 0) until the caller
 // says where
 static CfoBatchArgs cfo_stage1(const mimo_rx *h, const Capture &c) {
   CfoBatchArgs ca{};
   ca.iq = c.iq; ca.out = nullptr; ca.stride = c.stride; ca.frame_len = c.frame_len;
   ca.len = h->win_len + 64; ca.win = h->win_len; ca.N = h->N; ca.M = h->M; ca.cp = h->cp; ca.SL = h->SL;
-  ca.n_codes = h->N * h->nac; ca.n_data = h->pid + 2; ca.info = h->info.p;
-  ca.part = h->cfo_eps.p;
+  ca.n_codes = h->N * h->nac; ca.n_data = h->pid + 2; ca.info = h->ws.info.p;
+  ca.part = h->ws.cfo_eps.p;
   return ca;
 }
 
@@ -72,6 +72,7 @@ static DecodeRequest decode_request(const mimo_batch *b, const double *cfo_fold_
 // One batch, launched on s. Everything a stage reads of this batch travels in c and the
 // request aggregates, nothing in the handle, so an early return leaves no state behind.
 static int run_batch(mimo_rx *h, const mimo_batch *b, hipStream_t s) {
+  Workspace &w = h->ws;
   const uint32_t fpc = batch_fpc(b), slots = b->n_frames * fpc;
   const bool front = b->stages != MIMO_STAGES_DECODE, decode = b->stages != MIMO_STAGES_FRONT;
   Capture c{reinterpret_cast<const float2 *>(b->d_iq), b->stride, b->frame_len, 0, 1.0f};
@@ -89,21 +90,22 @@ static int run_batch(mimo_rx *h, const mimo_batch *b, hipStream_t s) {
     } else {
       if (front) {   // (a DECODE call reads what this batch's front half widened)
         const size_t need = (size_t)b->n_frames * h->N * b->stride;
-        if (h->wide.ensure(need) != hipSuccess) return fail(MIMO_ERR_NOMEM, "sc16 widening buffer");
+        if (w.grow(w.wide, need) != hipSuccess) return fail(MIMO_ERR_NOMEM, "sc16 widening buffer");
         hipEvent_t e = h->timer.begin(s);
-        const bool ok = launch_sc16_to_fc32(b->d_iq, b->stride, h->wide.p, b->stride,
+        const bool ok = launch_sc16_to_fc32(b->d_iq, b->stride, w.wide.p, b->stride,
                                             b->n_frames * h->N, b->frame_len, b->sc16_scale, s);
         h->timer.end(0, e, s);     // timed with the S&C stage (one extra launch)
         if (!ok) return fail(MIMO_ERR_ARG, "sc16 widening: bad geometry");
       }
-      c.iq = h->wide.p;
+      c.iq = w.wide.p;
       widened = true;
     }
   } else if (b->sample_format != MIMO_SAMPLE_FC32) {
     return fail(MIMO_ERR_ARG, "mimo_batch.sample_format must be MIMO_SAMPLE_FC32 or _SC16");
   }
   // The decode half of a batch whose front half this handle ran last. (Nothing checks that
-  // yet: a token handed from the FRONT call to its DECODE call would be verified here.)
+  // yet: a token handed from the FRONT call to its DECODE call would be verified here, and
+  // ws.gen is what it would compare.)
   if (!front) return run_decode(h, c, slots, decode_request(b, nullptr), s);
   SyncRequest sq{};
   sq.reset_trig = true;
@@ -118,7 +120,7 @@ static int run_batch(mimo_rx *h, const mimo_batch *b, hipStream_t s) {
   if (fold) {
     // opt-in CFO, folded: estimates only (stage 1 here, stage 2 after the search); the
     // search + LS loads and the decode derotate by them, no scratch capture
-    if (h->cfo_eps.ensure(cfo_batch_part_doubles(slots)) != hipSuccess)
+    if (w.grow(w.cfo_eps, cfo_batch_part_doubles(slots)) != hipSuccess)
       return fail(MIMO_ERR_NOMEM, "cfo estimate allocation failed");
     ca = cfo_stage1(h, c);
     ca.fold = 1;
@@ -128,13 +130,13 @@ static int run_batch(mimo_rx *h, const mimo_batch *b, hipStream_t s) {
     // weights and decode read (S&C ran on the raw samples: |P| and R do not depend on a
     // frequency offset)
     const size_t need = (size_t)b->n_frames * h->N * b->stride;
-    if (h->cfo_iq.ensure(need) != hipSuccess ||
-        h->cfo_eps.ensure(cfo_batch_part_doubles(slots)) != hipSuccess)
+    if (w.grow(w.cfo_iq, need) != hipSuccess ||
+        w.grow(w.cfo_eps, cfo_batch_part_doubles(slots)) != hipSuccess)
       return fail(MIMO_ERR_NOMEM, "cfo scratch allocation failed");
     ca = cfo_stage1(h, c);
-    ca.out = h->cfo_iq.p;
+    ca.out = w.cfo_iq.p;
     launch_cfo_batch(ca, slots, 1, s);
-    c.iq = h->cfo_iq.p;
+    c.iq = w.cfo_iq.p;
   }
   rc = run_estimate(h, c, slots, true, h->cfo ? &ca : nullptr, nullptr, s);
   if (rc) return rc;
@@ -143,19 +145,11 @@ static int run_batch(mimo_rx *h, const mimo_batch *b, hipStream_t s) {
   return decode ? run_decode(h, c, slots, decode_request(b, fold ? ca.part : nullptr), s) : MIMO_OK;
 }
 
-// The whole batch (14 launches and memsets) is captured into a HIP graph once a call repeats
-// the previous call's arguments, and replayed from then on: the grid shapes depend only on
-// the configuration and F (S&C items and hot items are pulled from device-side queues), so
-// the graph stays valid. Not used while stage timing or a diagnostic counter is on.
-// every device pointer a captured batch bakes into its kernels' arguments
-static std::array<const void *, 27> ws_signature(const mimo_rx *h) {
-  return {h->trig.p, h->keys.p, h->rec.p, h->info.p, h->G.p, h->W.p, h->gain.p, h->nvp.p,
-          h->evm_part.p, h->evm_out.p, h->n_exact.p, h->queue.p, h->hot.p, h->lspart.p,
-          h->tw, h->codes.codespec.p, h->scr_flag.p, h->scr_min.p, h->scr_max.p, h->nrec.p,
-          h->cand.p, h->certfail.p, h->lsq.p, h->cfo_iq.p, h->cfo_eps.p, h->wide.p,
-          h->spec.p};
-}
-
+// The whole batch (every launch and memset run_batch issues) is captured into a HIP graph once a
+// call repeats the previous call's arguments, and replayed from then on: the grid shapes depend
+// only on the configuration and F (S&C items and hot items are pulled from device-side queues),
+// so the graph stays valid while the workspace it points into has not moved: an entry carries
+// the ws.gen it was made at. Not used while stage timing or a diagnostic counter is on.
 static bool same_batch(const mimo_batch &x, const mimo_batch &y) {
   return x.d_iq == y.d_iq && x.stride == y.stride && x.frame_len == y.frame_len &&
          x.n_frames == y.n_frames && x.max_out_syms == y.max_out_syms &&
@@ -187,11 +181,10 @@ int mimo_rx_process_batch(mimo_rx *h, const mimo_batch *b, void *hip_stream) {
     return fail(MIMO_ERR_UNSUPPORTED, "cfo_correct with frames_per_capture > 1 needs the folded "
                                       "CFO path (fc32 C2/C3-type geometry, ref_mode 1)");
   hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
-  // the cache entry of this batch: same arguments, stream and workspace pointers
-  const auto sig = ws_signature(h);
+  // the cache entry of this batch: same arguments, stream and workspace generation
   mimo_rx::GraphEntry *hit = nullptr;
   for (auto &g : h->graphs)
-    if (g.used && same_batch(g.key, *b) && g.stream == s && g.sig == sig) hit = &g;
+    if (g.used && same_batch(g.key, *b) && g.stream == s && g.gen == h->ws.gen) hit = &g;
   int rc = MIMO_OK;
   if (diag_env().no_graph || h->timer.on) {
     rc = run_batch(h, b, s);
@@ -202,33 +195,26 @@ int mimo_rx_process_batch(mimo_rx *h, const mimo_batch *b, void *hip_stream) {
     // second identical call: workspace and one-time kernel attributes are settled; capture
     hit->used = ++h->graph_tick;
     hipGraph_t g = nullptr;
+    hipGraphExec_t ex = nullptr;
     HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
     rc = run_batch(h, b, s);
-    const hipError_t ec = hipStreamEndCapture(s, &g);
-    if (!rc && ec == hipSuccess && g) {
-      hipGraphExec_t ex = nullptr;
-      const bool inst = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) == hipSuccess;
-      (void)hipGraphDestroy(g);
-      if (inst && hit->sig == ws_signature(h)) {
-        hit->exec = ex;
-        HIPCHK(hipGraphLaunch(hit->exec, s));
-      } else {
-        if (inst) (void)hipGraphExecDestroy(ex);
-        *hit = mimo_rx::GraphEntry{};
-        rc = run_batch(h, b, s);
-      }
+    // kept only if the capture succeeded and the workspace did not move under it
+    bool ok = hipStreamEndCapture(s, &g) == hipSuccess && g && !rc && hit->gen == h->ws.gen;
+    ok = ok && hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) == hipSuccess;
+    if (g) (void)hipGraphDestroy(g);
+    if (ok) {
+      hit->exec = ex;
+      HIPCHK(hipGraphLaunch(hit->exec, s));
     } else {
-      if (g) (void)hipGraphDestroy(g);
       (void)hipGetLastError();
       *hit = mimo_rx::GraphEntry{};
-      if (!rc) rc = run_batch(h, b, s);   // capture failed: run directly
+      if (!rc) rc = run_batch(h, b, s);   // not captured: run directly
     }
   } else {
     rc = run_batch(h, b, s);
     // a workspace reallocation makes every earlier capture stale
-    const auto sig2 = ws_signature(h);
     for (auto &g : h->graphs)
-      if (g.used && g.sig != sig2) drop_graph(h, g);
+      if (g.used && g.gen != h->ws.gen) drop_graph(h, g);
     if (rc == MIMO_OK) {
       mimo_rx::GraphEntry *slot = &h->graphs[0];   // an empty or the least recently used slot
       for (auto &g : h->graphs)
@@ -236,7 +222,7 @@ int mimo_rx_process_batch(mimo_rx *h, const mimo_batch *b, void *hip_stream) {
       drop_graph(h, *slot);
       slot->key = *b;
       slot->stream = s;
-      slot->sig = sig2;
+      slot->gen = h->ws.gen;
       slot->used = ++h->graph_tick;
     }
   }
@@ -254,8 +240,8 @@ int mimo_rx_batch_results(mimo_rx *h, mimo_frame_result *out, uint32_t F) {
   std::vector<double> ev((size_t)F * h->N * 3);
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(inf.data(), h->info.p, sizeof(FrameInfo) * F, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(ev.data(), h->evm_out.p, sizeof(double) * ev.size(), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(inf.data(), h->ws.info.p, sizeof(FrameInfo) * F, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(ev.data(), h->ws.evm_out.p, sizeof(double) * ev.size(), hipMemcpyDeviceToHost));
   for (uint32_t f = 0; f < F; f++) {
     mimo_frame_result &r = out[f];
     std::memset(&r, 0, sizeof(r));
@@ -296,7 +282,7 @@ int mimo_rx_batch_G(mimo_rx *h, float *G, uint32_t F) {
   if (!h || !G) return fail(MIMO_ERR_ARG, "null argument");
   if (F > h->last_frames) return fail(MIMO_ERR_ARG, "more frames than the last batch");
   HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(G, h->G.p, sizeof(float2) * (size_t)F * h->M * h->N * h->N,
+  HIPCHK(hipMemcpy(G, h->ws.G.p, sizeof(float2) * (size_t)F * h->M * h->N * h->N,
                    hipMemcpyDeviceToHost));
   return MIMO_OK;
 }
@@ -319,7 +305,8 @@ static int launch_batch_mse(mimo_rx *h, uint32_t F, hipStream_t s) {
     return fail(MIMO_ERR_NOMEM, "post-detection MSE buffer");
   MseArgs m{};
   m.N = h->N; m.M = h->M; m.M_occ = h->M_occ;
-  m.occ_index = h->occ.p; m.G = h->G.p; m.W = h->W.p; m.gain = h->gain.p; m.info = h->info.p;
+  m.occ_index = h->occ.p; m.G = h->ws.G.p; m.W = h->ws.W.p; m.gain = h->ws.gain.p;
+  m.info = h->ws.info.p;
   m.nu = h->nu.p;
   if (!launch_mse(m, F, s)) return fail(MIMO_ERR_UNSUPPORTED, "no MSE kernel for this stream count");
   HIPCHK(hipGetLastError());
@@ -357,7 +344,7 @@ int mimo_rx_soft_demap(mimo_rx *h, const mimo_soft_demap *a, void *hip_stream) {
   k.bits = h->qam.b;
   k.qam_scale = h->qam.scale;
   k.llr_scale = a->llr_scale;
-  k.info = h->info.p;
+  k.info = h->ws.info.p;
   k.nu = h->nu.p;
   if (!launch_soft_demap(k, s)) return fail(MIMO_ERR_UNSUPPORTED, "no soft demapper for this QAM order");
   HIPCHK(hipGetLastError());

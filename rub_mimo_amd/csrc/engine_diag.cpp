@@ -46,7 +46,7 @@ int diag_sc_count(mimo_rx *h, uint32_t F, uint64_t nchunks, bool screen, uint32_
   (void)hipStreamIsCapturing(s, &cst);
   if (cst != hipStreamCaptureStatusNone) return MIMO_OK;
   uint32_t q[2] = {0, 0};
-  HIPCHK(hipMemcpyAsync(q, h->queue.p, sizeof(q), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(q, h->ws.queue.p, sizeof(q), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   fprintf(stderr, "sc_count hot_items %u (screen %d, frames %u, chunks %llu)\n", q[1],
           screen ? 1 : 0, F, (unsigned long long)nchunks);
@@ -54,10 +54,10 @@ int diag_sc_count(mimo_rx *h, uint32_t F, uint64_t nchunks, bool screen, uint32_
   const uint32_t n = std::min(q[1], hot_cap);
   std::vector<ScHot> hv(n);
   std::vector<unsigned long long> mn((size_t)F * nchunks), mx((size_t)F * nchunks);
-  HIPCHK(hipMemcpyAsync(hv.data(), h->hot.p, sizeof(ScHot) * n, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(mn.data(), h->scr_min.p, sizeof(unsigned long long) * mn.size(),
+  HIPCHK(hipMemcpyAsync(hv.data(), h->ws.hot.p, sizeof(ScHot) * n, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(mn.data(), h->ws.scr_min.p, sizeof(unsigned long long) * mn.size(),
                         hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(mx.data(), h->scr_max.p, sizeof(unsigned long long) * mx.size(),
+  HIPCHK(hipMemcpyAsync(mx.data(), h->ws.scr_max.p, sizeof(unsigned long long) * mx.size(),
                         hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   for (uint32_t i = 0; i < n; i++) {
@@ -145,7 +145,7 @@ int diag_dec_prof_report(mimo_rx *h, hipStream_t s) {
 int diag_cfo_frames(mimo_rx *h, uint32_t F, hipStream_t s) {
   if (!diag_env().cfo_debug || !h->cfo) return MIMO_OK;
   std::vector<FrameInfo> fi(F);
-  HIPCHK(hipMemcpyAsync(fi.data(), h->info.p, sizeof(FrameInfo) * F, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(fi.data(), h->ws.info.p, sizeof(FrameInfo) * F, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   for (uint32_t f = 0; f < F; f++)
     fprintf(stderr, "cfo_dbg f %u status %d base %lld i0 %u eps %.9f E %lld\n", f, (int)fi[f].status,

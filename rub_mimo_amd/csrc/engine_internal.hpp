@@ -2,7 +2,7 @@
 // mimo_rx / mimo_tx handles, the small host utilities, and the entry points of each file.
 //   engine.cpp         handles' life cycle, setters, plain getters, device/memcpy helpers
 //   engine_stages.cpp  workspace growth and the stage drivers (sync, estimate, decode)
-//   engine_batch.cpp   mimo_rx_process_batch: run_batch, the HIP-graph cache, batch getters
+//   engine_batch.cpp   mimo_rx_process_batch, the HIP-graph cache, batch getters, soft output
 //   engine_sic.cpp     mimo_rx_sic_detect, mimo_rx_sic_soft and the getters: the SIC passes
 //   engine_stream.cpp  mimo_rx_execute: the streaming framesync state machine, DEBUG_LOG
 //   engine_tx.cpp      transmitter, synthesiser, subcarrier-type and m-sequence helpers
@@ -60,6 +60,12 @@ struct DevBuf {
     if (e == hipSuccess) n = cnt;
     return e;
   }
+  // grow and keep: own the fresh block np (cnt elements); the caller has copied what survives
+  void adopt(T *np, size_t cnt) {
+    release();
+    p = np;
+    n = cnt;
+  }
 };
 
 inline int ilog2(uint32_t v) {
@@ -111,22 +117,56 @@ void set_capture(Args &a, const Capture &c) {
   a.sc16 = c.sc16; a.iq_scale = c.scale;
 }
 
+// The batch workspace. Rule: what run_batch can launch with lives in ws -- every device buffer
+// that a launch issued from run_batch or from the streaming execute's stages may reallocate
+// between calls. A captured batch graph holds these pointers in its kernel arguments, so they
+// move through grow() only (rec also in ensure_workspace, which bumps gen itself), and the
+// graph cache keys on gen (engine_batch.cpp). Sizes are computed next to the launches.
+struct Workspace {
+  uint64_t gen = 0;   // bumped exactly when a buffer below is (re)allocated
+  template <class T>
+  hipError_t grow(DevBuf<T> &b, size_t cnt) {
+    if (cnt <= b.n && b.p) return hipSuccess;
+    gen++;
+    return b.ensure(cnt);
+  }
+  // rec is [rec_frames][rec_stride] S&C chunk records; the per-frame arrays hold rec_frames too
+  uint32_t rec_frames = 0;
+  uint64_t rec_stride = 0;
+  DevBuf<unsigned long long> trig, keys;
+  DevBuf<ScRecord> rec;
+  DevBuf<FrameInfo> info;
+  DevBuf<float2> G, W;
+  DevBuf<float> gain;
+  DevBuf<double> nvp, evm_part, evm_out, evm_chunk, lspart;
+  DevBuf<uint32_t> evm_cnt;             // per-frame chunk counters of evm_kernel (self-resetting)
+  DevBuf<uint32_t> nrec;                // per-frame EVM records of the streaming decode
+  DevBuf<float2> lsq;                   // fused search + LS: X/S1 per access code
+  DevBuf<unsigned long long> n_exact;   // S&C exact fp32 recomputes (diagnostic)
+  DevBuf<uint32_t> queue;               // S&C work-queue head, hot-item count
+  DevBuf<ScHot> hot;                    // S&C items awaiting exact resolution
+  DevBuf<uint32_t> scr_flag;            // S&C screen: chunk listed [F][nchunks]
+  DevBuf<unsigned long long> scr_min, scr_max;   // first / last unproven position per chunk
+  DevBuf<unsigned long long> cand;      // streams: first S&C candidate per chunk [cap][chunks]
+  DevBuf<unsigned long long> certfail;  // streams: re-arm certificate failures [cap] (bit = slot)
+  DevBuf<float2> spec;                  // 8x8 split decode: spectra scratch
+  DevBuf<float2> wide;                  // sc16 batches the fused kernels do not take: widened
+  DevBuf<float2> cfo_iq;                // derotated scratch capture
+  DevBuf<double> cfo_eps;
+};
+
 }  // namespace mimo
 #pragma GCC visibility pop
 
 // ======================================================================================
 struct mimo_rx {
-  // configuration (framesync ctor arguments + config.h constants)
+  // ---- configuration (framesync ctor arguments + config.h constants) ----
   uint32_t M = 0, cp = 0, SL = 0, N = 0, nac = 0, pid = 0;
   uint32_t M_null = 0, M_pilot = 0, M_data = 0, M_occ = 0;
   int log2M = 0, log2F = 0;
   uint32_t F = 0, lagc = 0, n_lagc = 0, n_slots = 0;
   bool search_ls = false;               // fused search + LS (search_ls_kernel) for this geometry
   bool cfo = false;                     // opt-in CFO estimate + derotation (batched path)
-  DevBuf<float2> spec;                  // 8x8 split decode: spectra scratch
-  DevBuf<float2> wide;                  // sc16 batches the fused kernels do not take: widened
-  DevBuf<float2> cfo_iq;                // derotated scratch capture
-  DevBuf<double> cfo_eps;
   uint32_t n_cu = 256;
   int det = 0;
   float noise_var = -1.0f;
@@ -141,56 +181,33 @@ struct mimo_rx {
   std::vector<int32_t> occ_index;
   hipStream_t stream = nullptr;
   bool own_stream = false;
-  // device tables
+  // ---- device tables: written by mimo_rx_create, immutable for the handle's life ----
   float2 *tw = nullptr;
   Codes codes;
   DevBuf<float> vscale;
   DevBuf<int8_t> s1sign, s1sign_w;   // signs [N][nac][M]; ls_window_kernel's order
   DevBuf<int32_t> occ;
-  // workspace
-  uint32_t cap_frames = 0;
-  uint64_t cap_chunks = 0;
-  uint64_t cap_evm = 0;
-  DevBuf<unsigned long long> trig, keys;
-  DevBuf<ScRecord> rec;
-  DevBuf<FrameInfo> info;
-  DevBuf<float2> G, W;
-  DevBuf<float> gain;
-  DevBuf<double> nvp, evm_part, evm_out, lspart, evm_chunk;
-  DevBuf<float2> lsq;                   // fused search + LS: X/S1 per access code
-  DevBuf<uint32_t> evm_cnt;             // per-frame chunk counters of evm_kernel (self-resetting)
-  DevBuf<uint32_t> nrec;                // per-frame EVM records of the streaming decode
-  size_t cap_lspart = 0;
-  DevBuf<unsigned long long> n_exact;   // S&C exact fp32 recomputes (diagnostic)
-  DevBuf<uint32_t> queue;               // S&C work-queue head, hot-item count
-  DevBuf<ScHot> hot;                    // S&C items awaiting exact resolution
-  DevBuf<uint32_t> scr_flag;            // S&C screen: chunk listed [F][nchunks]
-  DevBuf<unsigned long long> scr_min, scr_max;   // first / last unproven position per chunk
-  DevBuf<unsigned long long> cand;      // streams: first S&C candidate per chunk [cap][chunks]
-  DevBuf<unsigned long long> certfail;  // streams: re-arm certificate failures [cap] (bit = slot)
-  uint32_t cap_hot = 0;
-  DevBuf<unsigned long long> sc_prof;   // RMIMO_SC_PROF=1 cycle counters
+  // ---- batch workspace: what run_batch can launch with lives in ws ----
+  Workspace ws;
+  // ---- last-batch facts and the post-pass buffers (in no captured graph) ----
   uint32_t last_frames = 0, last_max_out = 0;
   int last_decode_path = MIMO_DECODE_NONE;   // kernel family of the last decode launch
   int last_cfo_mode = 0;                     // CFO stages of the last batch (get_cfo_mode)
-  DevBuf<float> nu;                          // soft output: post-detection MSE [F][N][M_occ]
   uint32_t last_layout = 0;                  // out_layout of the last batch
+  DevBuf<float> nu;                          // soft output: post-detection MSE [F][N][M_occ]
   // SIC detection (engine_sic.cpp): tables T [F][N][N][M_occ], C [F][N(N-1)/2][M_occ], the
   // detection order [F][M_occ][N], the post-SIC MSE [F][N][M_occ] and the solved-carrier flags
   // [F][M_occ] of the last batch
   DevBuf<float2> sic_T, sic_C;
   DevBuf<uint8_t> sic_order, sic_ok;
   DevBuf<float> sic_nu;
-  // streaming state (facade). The device capture holds samples [origin, origin + total) of
-  // the stream since construction/reset (positions inside it are capture-relative).
+  // ---- streaming state (facade) and debug buffers (in no captured graph) ----
+  // The device capture holds samples [origin, origin + total) of the stream since
+  // construction/reset (positions inside it are capture-relative).
   DevBuf<float2> capbuf;
   uint64_t cap_len = 0, total = 0, origin = 0;
   uint64_t trim_clo = ~0ull;   // stream position of the S&C chunk of the last trim probe
   DevBuf<uint32_t> probe;               // trim probe: per antenna, a proven metric zero
-  // DEBUG_LOG files of the streaming execute (framing.cc:390-402, 598-600, 675-696, 873-883)
-  std::string dbg_dir;
-  std::vector<FILE *> dbg_fsc;
-  DevBuf<float> dbg_y, dbg_corr;
   int state = MIMO_STATE_SEEK_PLATEAU;
   uint64_t nsp = 0;
   bool have_sync = false, have_est = false;
@@ -199,13 +216,19 @@ struct mimo_rx {
   std::vector<float2> symhost;
   mimo_rx_symbol_cb cb = nullptr;
   void *user = nullptr;
+  // DEBUG_LOG files of the streaming execute (framing.cc:390-402, 598-600, 675-696, 873-883)
+  std::string dbg_dir;
+  std::vector<FILE *> dbg_fsc;
+  DevBuf<float> dbg_y, dbg_corr;
+  DevBuf<unsigned long long> sc_prof;   // RMIMO_SC_PROF=1 cycle counters
   StageTimer timer;
+  // ---- graph cache ----
   // captured batch pipelines (see mimo_rx_process_batch): a few recent batch keys, so that
   // callers alternating between capture buffers (double-buffered ingest) replay graphs too
   struct GraphEntry {
     mimo_batch key{};
     hipStream_t stream = nullptr;
-    std::array<const void *, 27> sig{};
+    uint64_t gen = 0;             // ws.gen the entry was recorded or captured at
     hipGraphExec_t exec = nullptr;
     uint64_t used = 0;            // 0: empty slot
   };
@@ -239,7 +262,7 @@ int copy_W(mimo_rx *h, uint32_t f, float *W);                            // fram
 int copy_corr(mimo_rx *h, uint32_t F, uint32_t *corr, uint32_t *s0);     // search argmax indices
 
 // ---- engine_stages.cpp ----
-int ensure_workspace(mimo_rx *h, uint32_t F, uint64_t chunks, uint64_t evm_entries);
+int ensure_workspace(mimo_rx *h, uint32_t F, uint64_t chunks);   // F slots, F x chunks records
 double sc_band(uint32_t M);
 // run_sync's optional inputs (the plain case: SyncRequest{} with fpc = 1)
 struct SyncRequest {

@@ -23,7 +23,7 @@ static int launch_batch_sic_tables(mimo_rx *h, uint32_t F, hipStream_t s) {
     return fail(MIMO_ERR_NOMEM, "SIC tables");
   SicTableArgs t{};
   t.N = h->N; t.M = h->M; t.M_occ = h->M_occ; t.detector = h->det;
-  t.occ_index = h->occ.p; t.G = h->G.p; t.info = h->info.p;
+  t.occ_index = h->occ.p; t.G = h->ws.G.p; t.info = h->ws.info.p;
   t.T = h->sic_T.p; t.C = h->sic_C.p; t.order = h->sic_order.p; t.nu = h->sic_nu.p;
   t.ok = h->sic_ok.p;
   if (!launch_sic_tables(t, F, s))
@@ -69,7 +69,7 @@ static int sic_pass(mimo_rx *h, const mimo_sic_soft *a, void *hip_stream) {
   k.N = h->N; k.M_occ = h->M_occ; k.max_out = a->max_out_syms;
   k.symbol_major = a->out_layout == MIMO_LAYOUT_SYMBOL_MAJOR;
   k.qam = h->qam;
-  k.info = h->info.p;
+  k.info = h->ws.info.p;
   k.T = h->sic_T.p; k.C = h->sic_C.p; k.order = h->sic_order.p;
   if (a->d_llr) {
     k.llr = a->d_llr;

@@ -9,40 +9,35 @@ namespace mimo {
 // Per-frame arrays grow with F; the per-chunk trigger records grow with F * chunks. A
 // growing single-frame record array (streaming capture) keeps its earlier records: chunks
 // already final are never recomputed, and trig[] is untouched when only the capture grows.
-int ensure_workspace(mimo_rx *h, uint32_t F, uint64_t chunks, uint64_t evm_entries) {
-  if (F > h->cap_frames) {
-    const uint32_t nf = F;
-    HIPCHK(h->trig.ensure(nf));
-    HIPCHK(h->keys.ensure((size_t)nf * h->N * h->n_slots));
-    HIPCHK(h->info.ensure(nf));
-    HIPCHK(h->G.ensure((size_t)nf * h->M * h->N * h->N));
-    HIPCHK(h->W.ensure((size_t)nf * h->M * h->N * h->N));
-    HIPCHK(h->gain.ensure((size_t)nf * h->M));
-    HIPCHK(h->nvp.ensure((size_t)nf * h->N * h->N * ((h->M + 255) / 256)));   // ls_combine blocks
-    HIPCHK(h->evm_out.ensure((size_t)nf * h->N * 3));
-    HIPCHK(h->evm_chunk.ensure((size_t)nf * kEvmChunks * h->N * 3));
-    HIPCHK(h->evm_cnt.ensure(nf));
-    HIPCHK(h->nrec.ensure(nf));
-    HIPCHK(hipMemset(h->evm_cnt.p, 0, sizeof(uint32_t) * nf));
-    h->cap_frames = nf;
-    HIPCHK(h->rec.ensure((size_t)nf * h->cap_chunks));
+int ensure_workspace(mimo_rx *h, uint32_t F, uint64_t chunks) {
+  Workspace &w = h->ws;
+  if (F > w.rec_frames) {
+    HIPCHK(w.grow(w.trig, F));
+    HIPCHK(w.grow(w.keys, (size_t)F * h->N * h->n_slots));
+    HIPCHK(w.grow(w.info, F));
+    HIPCHK(w.grow(w.G, (size_t)F * h->M * h->N * h->N));
+    HIPCHK(w.grow(w.W, (size_t)F * h->M * h->N * h->N));
+    HIPCHK(w.grow(w.gain, (size_t)F * h->M));
+    HIPCHK(w.grow(w.nvp, (size_t)F * h->N * h->N * ((h->M + 255) / 256)));   // ls_combine blocks
+    HIPCHK(w.grow(w.evm_out, (size_t)F * h->N * 3));
+    HIPCHK(w.grow(w.evm_chunk, (size_t)F * kEvmChunks * h->N * 3));
+    HIPCHK(w.grow(w.evm_cnt, F));
+    HIPCHK(w.grow(w.nrec, F));
+    HIPCHK(hipMemset(w.evm_cnt.p, 0, sizeof(uint32_t) * F));
+    w.rec_frames = F;
+    HIPCHK(w.grow(w.rec, (size_t)F * w.rec_stride));
   }
-  if (chunks > h->cap_chunks) {
-    const uint64_t nc = std::max<uint64_t>(chunks, h->cap_chunks * 2);
+  if (chunks > w.rec_stride) {
+    const uint64_t nc = std::max<uint64_t>(chunks, w.rec_stride * 2);
     ScRecord *np = nullptr;
-    HIPCHK(hipMalloc(&np, sizeof(ScRecord) * (size_t)h->cap_frames * nc));
+    HIPCHK(hipMalloc(&np, sizeof(ScRecord) * (size_t)w.rec_frames * nc));
     // frame 0's records survive: the streaming execute path (one frame) never recomputes a
     // final chunk, whatever batch sizes the handle ran before
-    if (h->rec.p && h->cap_chunks)
-      HIPCHK(hipMemcpy(np, h->rec.p, sizeof(ScRecord) * h->cap_chunks, hipMemcpyDeviceToDevice));
-    h->rec.release();
-    h->rec.p = np;
-    h->rec.n = (size_t)h->cap_frames * nc;
-    h->cap_chunks = nc;
-  }
-  if (evm_entries > h->cap_evm) {
-    HIPCHK(h->evm_part.ensure(evm_entries));
-    h->cap_evm = evm_entries;
+    if (w.rec.p && w.rec_stride)
+      HIPCHK(hipMemcpy(np, w.rec.p, sizeof(ScRecord) * w.rec_stride, hipMemcpyDeviceToDevice));
+    w.rec.adopt(np, (size_t)w.rec_frames * nc);
+    w.gen++;
+    w.rec_stride = nc;
   }
   return MIMO_OK;
 }
@@ -63,7 +58,8 @@ int run_sync(mimo_rx *h, const Capture &c, uint32_t F, const SyncRequest &q, hip
   const uint64_t nchunks = (c.frame_len + K - 1) / K, chunk_lo = q.chunk_lo;
   const uint32_t fpc = q.fpc;
   const bool stream = fpc > 1;
-  int rc = ensure_workspace(h, F * fpc, nchunks, 0);
+  Workspace &w = h->ws;
+  int rc = ensure_workspace(h, F * fpc, nchunks);
   if (rc) return rc;
   FillArgs fa{};
   auto add_fill = [&fa](void *p, uint64_t bytes, uint32_t v) {
@@ -72,14 +68,14 @@ int run_sync(mimo_rx *h, const Capture &c, uint32_t F, const SyncRequest &q, hip
     fa.v[fa.count] = v;
     fa.count++;
   };
-  if (q.reset_trig) add_fill(h->trig.p, sizeof(unsigned long long) * F, 0xFFFFFFFFu);
+  if (q.reset_trig) add_fill(w.trig.p, sizeof(unsigned long long) * F, 0xFFFFFFFFu);
   // the search's argmax keys, zeroed here instead of by a memset ahead of the search
-  if (q.zero_keys) add_fill(h->keys.p, sizeof(unsigned long long) * F * fpc * h->N * h->n_slots, 0u);
+  if (q.zero_keys) add_fill(w.keys.p, sizeof(unsigned long long) * F * fpc * h->N * h->n_slots, 0u);
   if (stream) {
-    HIPCHK(h->cand.ensure((size_t)F * nchunks));
-    HIPCHK(h->certfail.ensure(F));
-    add_fill(h->cand.p, sizeof(unsigned long long) * F * nchunks, 0xFFFFFFFFu);
-    add_fill(h->certfail.p, sizeof(unsigned long long) * F, 0u);
+    HIPCHK(w.grow(w.cand, (size_t)F * nchunks));
+    HIPCHK(w.grow(w.certfail, F));
+    add_fill(w.cand.p, sizeof(unsigned long long) * F * nchunks, 0xFFFFFFFFu);
+    add_fill(w.certfail.p, sizeof(unsigned long long) * F, 0u);
   }
   if (chunk_lo >= nchunks) launch_fill(fa, s);
   if (chunk_lo < nchunks) {
@@ -90,40 +86,37 @@ int run_sync(mimo_rx *h, const Capture &c, uint32_t F, const SyncRequest &q, hip
     a.band = sc_band(h->M);
     a.diag = (uint32_t)diag_env().sc_diag;
     a.chunk_len = K; a.chunk_lo = chunk_lo; a.chunk_hi = nchunks;
-    a.trig = h->trig.p; a.rec = h->rec.p; a.rec_stride = h->cap_chunks;
-    a.cand = stream ? h->cand.p : nullptr;
+    a.trig = w.trig.p; a.rec = w.rec.p; a.rec_stride = w.rec_stride;
+    a.cand = stream ? w.cand.p : nullptr;
     a.no_skip = stream ? 1 : 0;
-    if (!h->n_exact.p) {
-      HIPCHK(h->n_exact.ensure(1));
-      HIPCHK(hipMemsetAsync(h->n_exact.p, 0, sizeof(unsigned long long), s));
+    if (!w.n_exact.p) {
+      HIPCHK(w.grow(w.n_exact, 1));
+      HIPCHK(hipMemsetAsync(w.n_exact.p, 0, sizeof(unsigned long long), s));
     }
-    a.n_exact = h->n_exact.p;
-    if (!h->queue.p) HIPCHK(h->queue.ensure(3));
-    add_fill(h->queue.p, 3 * sizeof(uint32_t), 0u);
-    a.queue = h->queue.p;
-    a.hot_count = h->queue.p + 1;
+    a.n_exact = w.n_exact.p;
+    if (!w.queue.p) HIPCHK(w.grow(w.queue, 3));
+    add_fill(w.queue.p, 3 * sizeof(uint32_t), 0u);
+    a.queue = w.queue.p;
+    a.hot_count = w.queue.p + 1;
     // screened path where the geometry allows it (else the per-chunk item kernel): one hot item
     // per listed chunk
     const bool screen = sc_screen_ok(h->M);
     const uint64_t n_list = (nchunks - chunk_lo) * (uint64_t)F;
     const uint32_t hot_cap = screen ? (uint32_t)n_list : 8 * F + 32;
-    if (hot_cap > h->cap_hot) {
-      HIPCHK(h->hot.ensure(hot_cap));
-      h->cap_hot = hot_cap;
-    }
+    HIPCHK(w.grow(w.hot, hot_cap));
     a.nchunks = nchunks;
     if (screen) {
       const size_t nf = (size_t)F * nchunks;
-      HIPCHK(h->scr_flag.ensure(nf));
-      HIPCHK(h->scr_min.ensure(nf));
-      HIPCHK(h->scr_max.ensure(nf));
-      add_fill(h->scr_flag.p, sizeof(uint32_t) * nf, 0u);
-      add_fill(h->scr_min.p, sizeof(unsigned long long) * nf, 0xFFFFFFFFu);
-      add_fill(h->scr_max.p, sizeof(unsigned long long) * nf, 0u);
-      a.fmin = h->scr_min.p;
-      a.fmax = h->scr_max.p;
+      HIPCHK(w.grow(w.scr_flag, nf));
+      HIPCHK(w.grow(w.scr_min, nf));
+      HIPCHK(w.grow(w.scr_max, nf));
+      add_fill(w.scr_flag.p, sizeof(uint32_t) * nf, 0u);
+      add_fill(w.scr_min.p, sizeof(unsigned long long) * nf, 0xFFFFFFFFu);
+      add_fill(w.scr_max.p, sizeof(unsigned long long) * nf, 0u);
+      a.fmin = w.scr_min.p;
+      a.fmax = w.scr_max.p;
     }
-    a.hot = h->hot.p;
+    a.hot = w.hot.p;
     a.hot_cap = hot_cap;
     launch_fill(fa, s);   // trigger words, queue heads and screen flags in one launch
     if ((rc = diag_sc_prof_arm(h, screen, s, &a.prof))) return rc;
@@ -134,7 +127,7 @@ int run_sync(mimo_rx *h, const Capture &c, uint32_t F, const SyncRequest &q, hip
       sa.N = h->N; sa.M = h->M;
       sa.thr_screen = h->thr - 0.01;
       sa.chunk_len = K; sa.chunk_lo = chunk_lo; sa.nchunks = nchunks;
-      sa.flag = h->scr_flag.p; sa.fmin = h->scr_min.p; sa.fmax = h->scr_max.p;
+      sa.flag = w.scr_flag.p; sa.fmin = w.scr_min.p; sa.fmax = w.scr_max.p;
       sa.count = a.hot_count; sa.hot = a.hot; sa.cap = a.hot_cap;
       // batches: every capture starts at its (first) framesync's origin; the streaming execute's
       // capture may begin mid-stream after a trim (its history is not empty)
@@ -156,16 +149,16 @@ int run_sync(mimo_rx *h, const Capture &c, uint32_t F, const SyncRequest &q, hip
       sa.chunk_hi = c1;
       launch_sc_screen(sa, F, s);
       ScArgs a1 = a;
-      if (c1 < nchunks) a1.snap = h->queue.p + 2;   // phase-1 items: done after this launch
+      if (c1 < nchunks) a1.snap = w.queue.p + 2;   // phase-1 items: done after this launch
       launch_sc_exact(a1, s);   // resolves and finalises its items itself
       if (a.diag & 32) launch_sc_finalize(a, s);
       if (c1 < nchunks) {
         sa.chunk_lo = c1;
         sa.chunk_hi = nchunks;
-        sa.trig = h->trig.p;
+        sa.trig = w.trig.p;
         launch_sc_screen(sa, F, s);
         ScArgs a2 = a;
-        a2.item_lo = h->queue.p + 2;
+        a2.item_lo = w.queue.p + 2;
         launch_sc_exact(a2, s);
         if (a.diag & 32) launch_sc_finalize(a2, s);
       }
@@ -179,13 +172,13 @@ int run_sync(mimo_rx *h, const Capture &c, uint32_t F, const SyncRequest &q, hip
   }
   PlateauArgs pa{};
   set_capture(pa, c);
-  pa.trig = h->trig.p; pa.rec = h->rec.p; pa.rec_stride = h->cap_chunks; pa.chunk_len = K;
+  pa.trig = w.trig.p; pa.rec = w.rec.p; pa.rec_stride = w.rec_stride; pa.chunk_len = K;
   pa.N = h->N; pa.M = h->M; pa.SL = h->SL; pa.thr = h->thr; pa.win_len = h->win_len;
   pa.band = sc_band(h->M);
-  pa.info = h->info.p;
+  pa.info = w.info.p;
   pa.fpc = fpc; pa.nchunks = nchunks;
-  pa.cand = stream ? h->cand.p : nullptr;
-  pa.certfail = stream ? h->certfail.p : nullptr;
+  pa.cand = stream ? w.cand.p : nullptr;
+  pa.certfail = stream ? w.certfail.p : nullptr;
   pa.ref_starts = q.ref_starts;
   pa.ref_stride = q.ref_stride ? q.ref_stride : fpc;
   hipEvent_t e = h->timer.begin(s);
@@ -198,28 +191,29 @@ int run_sync(mimo_rx *h, const Capture &c, uint32_t F, const SyncRequest &q, hip
 
 int run_estimate(mimo_rx *h, const Capture &c, uint32_t F, bool keys_zeroed, CfoBatchArgs *cfo,
                  float *corr_trace, hipStream_t s) {
+  Workspace &w = h->ws;
   if (!keys_zeroed)
-    HIPCHK(hipMemsetAsync(h->keys.p, 0, sizeof(unsigned long long) * F * h->N * h->n_slots, s));
+    HIPCHK(hipMemsetAsync(w.keys.p, 0, sizeof(unsigned long long) * F * h->N * h->n_slots, s));
   SearchArgs sa{};
   set_capture(sa, c);
   sa.N = h->N; sa.M = h->M; sa.SL = h->SL; sa.n_slots = h->n_slots;
   sa.lagc = h->lagc; sa.n_lagc = h->n_lagc;
   sa.codespec = h->codes.codespec.p; sa.vscale = h->vscale.p;
   sa.codespec_w = h->codes.codespec_w.p;
-  sa.info = h->info.p; sa.keys = h->keys.p; sa.tw = h->tw;
+  sa.info = w.info.p; sa.keys = w.keys.p; sa.tw = h->tw;
   sa.corr_trace = corr_trace;
   LsArgs la{};
   set_capture(la, c);
   la.N = h->N; la.M = h->M; la.nac = h->nac; la.n_slots = h->n_slots;
-  la.keys = h->keys.p; la.s1sign = h->s1sign.p; la.occ_index = h->occ.p;
+  la.keys = w.keys.p; la.s1sign = h->s1sign.p; la.occ_index = h->occ.p;
   la.s1sign_w = h->s1sign_w.p;
-  la.keep_bias = h->keep_bias; la.scale = h->ls_scale; la.info = h->info.p;
+  la.keep_bias = h->keep_bias; la.scale = h->ls_scale; la.info = w.info.p;
   la.n_groups = (h->nac + kLsCodesPerGroup - 1) / kLsCodesPerGroup;
   la.n_nvp = h->N * h->N * ((h->M + 255) / 256);
-  la.G = h->G.p; la.nv_part = h->nvp.p; la.tw = h->tw;
+  la.G = w.G.p; la.nv_part = w.nvp.p; la.tw = h->tw;
   // opt-in CFO stage 2 after the search: the residual from the data prefixes
   auto cfo_stage2 = [&](int rot_window) {
-    cfo->keys = h->keys.p; cfo->n_slots = h->n_slots; cfo->rot_window = rot_window;
+    cfo->keys = w.keys.p; cfo->n_slots = h->n_slots; cfo->rot_window = rot_window;
     launch_cfo_batch(*cfo, F, 2, s);
   };
   if (h->search_ls) {
@@ -230,9 +224,9 @@ int run_estimate(mimo_rx *h, const Capture &c, uint32_t F, bool keys_zeroed, Cfo
     // parity tests' reference for the window form
     const bool ls_win = !diag_env().ls_terms && ls_window_supported(h->log2M, h->nac, cfo != nullptr);
     if (!ls_win) {
-      HIPCHK(h->lsq.ensure((size_t)F * h->N * h->N * h->nac * h->M));
-      sa.s1sign = h->s1sign.p; sa.lsq = h->lsq.p; sa.nac = h->nac;
-      la.lsq = h->lsq.p;
+      HIPCHK(w.grow(w.lsq, (size_t)F * h->N * h->N * h->nac * h->M));
+      sa.s1sign = h->s1sign.p; sa.lsq = w.lsq.p; sa.nac = h->nac;
+      la.lsq = w.lsq.p;
     }
     sa.xcd_order = 1;
     sa.cfo_part = (cfo && cfo->fold) ? cfo->part : nullptr;   // folded CFO: derotating loads
@@ -254,12 +248,8 @@ int run_estimate(mimo_rx *h, const Capture &c, uint32_t F, bool keys_zeroed, Cfo
     launch_search(sa, h->log2F, F, s);
     h->timer.end(2, e, s);
     if (cfo) cfo_stage2(1);   // before a separate LS pass: the whole window in place
-    const size_t need = (size_t)F * h->N * h->N * la.n_groups * 3 * h->M;
-    if (need > h->cap_lspart) {
-      HIPCHK(h->lspart.ensure(need));
-      h->cap_lspart = need;
-    }
-    la.part = h->lspart.p;
+    HIPCHK(w.grow(w.lspart, (size_t)F * h->N * h->N * la.n_groups * 3 * h->M));
+    la.part = w.lspart.p;
     e = h->timer.begin(s);
     launch_ls(la, h->log2M, F, s);
     h->timer.end(3, e, s);
@@ -267,10 +257,10 @@ int run_estimate(mimo_rx *h, const Capture &c, uint32_t F, bool keys_zeroed, Cfo
   WeightArgs wa{};
   wa.N = h->N; wa.M = h->M; wa.M_occ = h->M_occ; wa.nac = h->nac; wa.SL = h->SL;
   wa.n_slots = h->n_slots; wa.detector = h->det; wa.noise_var = h->noise_var;
-  wa.nv_norm = h->nv_norm; wa.occ_index = h->occ.p; wa.G = h->G.p; wa.W = h->W.p;
-  wa.gain = h->gain.p; wa.nv_part = h->nvp.p; wa.n_nvp = la.n_nvp; wa.keys = h->keys.p;
+  wa.nv_norm = h->nv_norm; wa.occ_index = h->occ.p; wa.G = w.G.p; wa.W = w.W.p;
+  wa.gain = w.gain.p; wa.nv_part = w.nvp.p; wa.n_nvp = la.n_nvp; wa.keys = w.keys.p;
   wa.win_len = h->win_len;
-  wa.info = h->info.p;
+  wa.info = w.info.p;
   hipEvent_t e = h->timer.begin(s);
   launch_weights(wa, F, s);
   h->timer.end(4, e, s);
@@ -279,13 +269,15 @@ int run_estimate(mimo_rx *h, const Capture &c, uint32_t F, bool keys_zeroed, Cfo
 }
 
 int run_decode(mimo_rx *h, const Capture &c, uint32_t F, const DecodeRequest &q, hipStream_t s) {
+  Workspace &w = h->ws;
   const uint32_t max_out = q.max_out;
-  if (max_out == 0) return ensure_workspace(h, F, 0, 0);
+  int rc = ensure_workspace(h, F, 0);
+  if (rc || max_out == 0) return rc;
   DecodeArgs d{};
   set_capture(d, c);
   d.N = h->N; d.M = h->M; d.cp = h->cp; d.SL = h->SL; d.M_occ = h->M_occ;
   d.detector = h->det; d.siso_tx = h->siso_tx; d.siso_rx = h->siso_rx; d.dn = h->dn;
-  d.occ_index = h->occ.p; d.W = h->W.p; d.gain = h->gain.p; d.G = h->G.p; d.info = h->info.p;
+  d.occ_index = h->occ.p; d.W = w.W.p; d.gain = w.gain.p; d.G = w.G.p; d.info = w.info.p;
   d.max_out = max_out; d.out_sym = q.out_sym; d.out_idx = q.out_idx;
   if (q.layout == MIMO_LAYOUT_SYMBOL_MAJOR) {   // [F][max_out][N][M_occ]
     d.o_ts = h->M_occ;
@@ -296,27 +288,25 @@ int run_decode(mimo_rx *h, const Capture &c, uint32_t F, const DecodeRequest &q,
   }
   d.ref_mode = q.ref_mode; d.ref_idx = q.ref_idx; d.ref_seed = q.ref_seed;
   d.frame_id0 = q.frame_id0;
-  d.qam = h->qam; d.evm_part = h->evm_part.p; d.tw = h->tw;
+  d.qam = h->qam; d.tw = h->tw;
   d.n_frames = F; d.n_cu = h->n_cu;
   d.n_caps = q.n_caps ? q.n_caps : F; d.n_refs = F;
   d.all_occ = (h->M_occ == h->M) ? 1 : 0;
-  int rc = diag_dec_prof_arm(h, s, &d.prof);
-  if (rc) return rc;
+  if ((rc = diag_dec_prof_arm(h, s, &d.prof))) return rc;
   hipEvent_t e = h->timer.begin(s);
-  d.nrec = h->nrec.p;
+  d.nrec = w.nrec.p;
   d.cpe = h->cfo ? (q.cfo_fold_part ? 2 : 1) : 0;
   d.cfo_part = q.cfo_fold_part;
   d.rec_stride = max_out;
   if (decode_split_accepts(d, h->log2M)) {
     // [F][group][N][M] complex64 spectra of the 8x8 split decode (one symbol group)
-    if (h->spec.ensure((size_t)F * split_group_symbols(max_out) * h->N * h->M) != hipSuccess)
+    if (w.grow(w.spec, (size_t)F * split_group_symbols(max_out) * h->N * h->M) != hipSuccess)
       return fail(MIMO_ERR_NOMEM, "split decode scratch");
-    d.spec = h->spec.p;
+    d.spec = w.spec.p;
     d.rec_stride = std::max(d.rec_stride, split_plan(max_out, h->log2M, nullptr, nullptr));
   }
-  rc = ensure_workspace(h, F, 0, (uint64_t)F * d.rec_stride * h->N * 3 * kMaxEvmParts);
-  if (rc) return rc;
-  d.evm_part = h->evm_part.p;
+  HIPCHK(w.grow(w.evm_part, (size_t)F * d.rec_stride * h->N * 3 * kMaxEvmParts));
+  d.evm_part = w.evm_part.p;
   bool per_frame = false;
   int path = MIMO_DECODE_NONE;
   const uint32_t parts = launch_decode(d, h->log2M, F, s, &per_frame, &path);
@@ -328,13 +318,13 @@ int run_decode(mimo_rx *h, const Capture &c, uint32_t F, const DecodeRequest &q,
     return fail(MIMO_ERR_UNSUPPORTED, "no decode kernel takes this configuration");
   if ((rc = diag_dec_prof_report(h, s))) return rc;
   EvmArgs ea{};
-  ea.N = h->N; ea.max_out = max_out; ea.parts = parts; ea.info = h->info.p;
-  ea.evm_part = h->evm_part.p;
+  ea.N = h->N; ea.max_out = max_out; ea.parts = parts; ea.info = w.info.p;
+  ea.evm_part = w.evm_part.p;
   ea.rec_stride = d.rec_stride;
-  ea.evm_out = h->evm_out.p;
-  ea.chunk_part = h->evm_chunk.p;
-  ea.counter = h->evm_cnt.p;
-  ea.nrec = per_frame ? h->nrec.p : nullptr;
+  ea.evm_out = w.evm_out.p;
+  ea.chunk_part = w.evm_chunk.p;
+  ea.counter = w.evm_cnt.p;
+  ea.nrec = per_frame ? w.nrec.p : nullptr;
   // per workgroup segment (streaming, residue-class), not per chunk x range
   ea.few = (path == MIMO_DECODE_STREAM) ? 1 : 0;
   e = h->timer.begin(s);

@@ -21,9 +21,7 @@ static int grow_capture(mimo_rx *h, uint64_t need) {
                             sizeof(float2) * h->total, h->N, hipMemcpyDeviceToDevice, h->stream));
   }
   HIPCHK(hipStreamSynchronize(h->stream));
-  h->capbuf.release();
-  h->capbuf.p = np;
-  h->capbuf.n = nc * h->N;
+  h->capbuf.adopt(np, nc * h->N);
   h->cap_len = nc;
   return MIMO_OK;
 }
@@ -59,7 +57,7 @@ static int finish_estimate(mimo_rx *h) {
   // the window is complete: the device frame record says so (the plateau kernel saw it
   // incomplete when the trigger fired)
   h->sinfo.status = MIMO_FRAME_OK;
-  HIPCHK(hipMemcpyAsync(h->info.p, &h->sinfo, sizeof(FrameInfo), hipMemcpyHostToDevice,
+  HIPCHK(hipMemcpyAsync(h->ws.info.p, &h->sinfo, sizeof(FrameInfo), hipMemcpyHostToDevice,
                         h->stream));
   float *corr_trace = nullptr;
   if (!h->dbg_dir.empty()) {
@@ -69,7 +67,7 @@ static int finish_estimate(mimo_rx *h) {
   }
   int rc = run_estimate(h, c, 1, false, nullptr, corr_trace, h->stream);
   if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(&h->sinfo, h->info.p, sizeof(FrameInfo), hipMemcpyDeviceToHost,
+  HIPCHK(hipMemcpyAsync(&h->sinfo, h->ws.info.p, sizeof(FrameInfo), hipMemcpyDeviceToHost,
                         h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   if (!h->dbg_dir.empty() && (rc = write_corr_logs(h))) return rc;
@@ -203,9 +201,7 @@ static int rebase_to_window(mimo_rx *h, uint64_t piece) {
     HIPCHK(hipMemcpy2DAsync(np, sizeof(float2) * nc, h->capbuf.p + D, sizeof(float2) * h->cap_len,
                             sizeof(float2) * keep, h->N, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  h->capbuf.release();
-  h->capbuf.p = np;
-  h->capbuf.n = nc * h->N;
+  h->capbuf.adopt(np, nc * h->N);
   h->cap_len = nc;
   h->origin += (uint64_t)D;
   h->total = keep;
@@ -237,17 +233,17 @@ static int execute_piece(mimo_rx *h, const float *const *iq, uint64_t off, uint6
   h->total = old_total + n;
   if (h->state == MIMO_STATE_SEEK_PLATEAU) {
     const uint64_t K = sc_chunk_len(h->cp);
-    rc = ensure_workspace(h, 1, (h->total + K - 1) / K, 0);
+    rc = ensure_workspace(h, 1, (h->total + K - 1) / K);
     if (rc) return rc;
     if (old_total == 0 && h->origin == 0)
-      HIPCHK(hipMemsetAsync(h->trig.p, 0xFF, sizeof(unsigned long long), h->stream));
+      HIPCHK(hipMemsetAsync(h->ws.trig.p, 0xFF, sizeof(unsigned long long), h->stream));
     // re-run the partially filled chunk; earlier chunks are final (y[n] uses x[<=n] only)
     SyncRequest q{};
     q.chunk_lo = old_total / K;
     q.fpc = 1;
     rc = run_sync(h, Capture{h->capbuf.p, h->cap_len, h->total, 0, 1.0f}, 1, q, h->stream);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(&h->sinfo, h->info.p, sizeof(FrameInfo), hipMemcpyDeviceToHost,
+    HIPCHK(hipMemcpyAsync(&h->sinfo, h->ws.info.p, sizeof(FrameInfo), hipMemcpyDeviceToHost,
                           h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (!h->dbg_fsc.empty()) {

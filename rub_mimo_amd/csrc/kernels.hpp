@@ -113,8 +113,8 @@ void launch_sc_screen(const ScreenArgs &a, uint32_t n_frames, hipStream_t s);
 void launch_sc_exact(const ScArgs &a, hipStream_t s);
 // persistent grid of n_cu x (resident blocks per CU) over the F x chunks items
 void launch_sc(const ScArgs &a, uint32_t n_frames, uint32_t n_cu, hipStream_t s);
-void launch_sc_hot(const ScArgs &a, hipStream_t s);
-void launch_sc_finalize(const ScArgs &a, hipStream_t s);   // plateau rule per hot item   // resolve + finalize the hot items
+void launch_sc_hot(const ScArgs &a, hipStream_t s);        // resolve + finalize the hot items
+void launch_sc_finalize(const ScArgs &a, hipStream_t s);   // plateau rule per hot item
 
 struct PlateauArgs {
   const unsigned long long *trig;
@@ -312,11 +312,12 @@ bool decode_stream_cpe(const DecodeArgs &a);
 // alternating over symbol groups); 0 when the configuration is not handled or a.spec is null.
 // The scratch holds split_group_symbols(max_out) symbols per frame.
 uint32_t launch_decode_split(const DecodeArgs &a, int log2M, uint32_t n_frames, hipStream_t s);
-// one-pass 8x8 decode by residue class (M = 4096): accepts / launches (0: not handled), and
-// the EVM records per frame it may write (rec_stride must hold them)
+// true when launch_decode_split takes this configuration (a.spec aside): 8 streams, every
+// carrier occupied, 512 <= M <= 4096, at least M/64 symbols
 bool decode_split_accepts(const DecodeArgs &a, int log2M);
 uint32_t split_group_symbols(uint32_t max_out);
-// the split decode's symbol groups, symbol ranges per (group, chunk) and EVM records per frame
+// the split decode's symbol groups, symbol ranges per (group, chunk) and the EVM records per
+// frame it may write (rec_stride must hold them)
 uint32_t split_plan(uint32_t max_out, int log2M, uint32_t *groups, uint32_t *P);
 constexpr uint32_t kMaxEvmParts = 16;
 constexpr uint32_t kStreamMaxQam = 256;   // constellation points the LDS tables hold (256-QAM)
@@ -454,17 +455,17 @@ struct MixArgs {
 };
 void launch_mix(const MixArgs &a, uint32_t n_frames, hipStream_t s);
 
-// sc16 wire samples (interleaved int16 I/Q) -> planar complex64 rows (ingest_kernels.hip);
-// false when the grid would not fit
 // CFO (cfo_kernels.hip): per-row sum conj(x[n]) x[n+half] over [start, start+half) into
 // d_out[2*row..], fp64; derotation by exp(-j 2 pi nu (n - n0))
 bool launch_cfo_corr(const void *x, uint64_t stride, uint32_t rows, uint64_t start,
                      uint32_t half, double *d_out, hipStream_t s);
 bool launch_cfo_derotate(void *x, uint64_t stride, uint32_t rows, uint64_t n, int64_t n0,
                          double nu, hipStream_t s);
-// host side: record msg as this thread's mimo_last_error() and return code (engine.cpp)
+// host side, defined in engine.cpp: record msg as this thread's mimo_last_error(), return code
 int host_fail(int code, const char *msg);
 
+// sc16 wire samples (interleaved int16 I/Q) -> planar complex64 rows (ingest_kernels.hip);
+// false when the grid would not fit
 bool launch_sc16_to_fc32(const void *src, uint64_t src_stride, void *dst, uint64_t dst_stride,
                          uint32_t rows, uint64_t n, float scale, hipStream_t s);
 

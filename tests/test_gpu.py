@@ -434,6 +434,73 @@ def test_alternating_capture_buffers_replay_their_own_graphs():
     assert not torch.equal(seen[0][0][0], seen[1][0][0])
 
 
+@pytest.mark.parametrize("kind", ["frames", "chunks", "symbols"])
+def test_workspace_growth_drops_stale_graphs(kind):
+    """A batch that reallocates the engine's workspace after a graph of a smaller batch exists:
+    the small batch's graph points into freed buffers and must not be replayed (the graph cache
+    keys on the workspace generation, engine_batch.cpp). Phase A runs the small batch four times
+    (direct, capture, replay, replay), phase B three calls of a batch that grows the per-frame
+    arrays (frames), the S&C records and screen lists (chunks: a longer capture) or the EVM
+    partials (symbols), phase C the small batch four more times. Every A and C call is bitwise
+    equal, the B calls are bitwise equal to each other, and B agrees with A where the batches
+    overlap."""
+    import torch
+    M, cp, N, nac, pid, F, FB, mo, moB, tail = 256, 19, 4, 4, 24, 2, 5, 8, 24, 2 * 16384
+    sp = SynthParams(M=M, cp_len=cp, num_streams=N, num_access_codes=nac, pid=pid,
+                     qam_order=16, seed=21, snr_db=30.0)
+    L = sp.max_frame_len()
+    iq = torch.empty((FB, N, L), dtype=torch.complex64, device="cuda")
+    Synthesizer(sp).generate(iq, L, L, FB, frame_id0=0)
+    rx = Receiver(RxParams(M=M, cp_len=cp, num_streams=N, num_access_codes=nac, pid_max=pid,
+                           detector=_lib.DET_MMSE, qam_order=16))
+    mocc = rx.M_occ
+    a_in = dict(iq=iq, L=L, F=F, mo=mo)
+    if kind == "frames":
+        b_in = dict(a_in, F=FB)
+    elif kind == "chunks":   # the same two frames, then an idle radio: zeros
+        long_iq = torch.zeros((F, N, L + tail), dtype=torch.complex64, device="cuda")
+        long_iq[:, :, :L] = iq[:F]
+        b_in = dict(a_in, iq=long_iq, L=L + tail)
+    else:
+        b_in = dict(a_in, mo=moB)
+
+    def run(a, calls, bufs=None):
+        shape = (a["F"], N, a["mo"], mocc)
+        sym, idx = bufs or (torch.empty(shape, dtype=torch.complex64, device="cuda"),
+                            torch.empty(shape, dtype=torch.uint8, device="cuda"))
+        outs = []
+        for _ in range(calls):
+            sym.zero_()
+            idx.zero_()
+            rx.process(a["iq"], a["L"], a["L"], a["F"], max_out=a["mo"], out_sym=sym,
+                       out_idx=idx, ref_mode=2, ref_seed=21)
+            torch.cuda.synchronize()
+            res = [(r["status"], r["sync_index"], float(np.sum(r["evm_num"])))
+                   for r in rx.results()]
+            outs.append((sym.clone(), idx.clone(), res, rx.corr()))
+        return outs, (sym, idx)
+
+    def same(x, y):
+        return torch.equal(x[0], y[0]) and torch.equal(x[1], y[1]) and x[2] == y[2]
+
+    A, bufs = run(a_in, 4)
+    assert all(r[0] == _lib.FRAME_OK for r in A[0][2]) and A[0][0].abs().max() > 0
+    B, _ = run(b_in, 3)
+    C_, _ = run(a_in, 4, bufs)   # phase A's arguments, output buffers included
+    for o in A[1:] + C_:
+        assert same(o, A[0])
+    for o in B[1:]:
+        assert same(o, B[0])
+    if kind == "frames":
+        assert [t[:2] for t in B[0][2][:F]] == [t[:2] for t in A[0][2]]
+        for x, y in zip(B[0][3], A[0][3]):
+            assert np.array_equal(x[:F], y)
+    elif kind == "chunks":
+        assert [t[:2] for t in B[0][2]] == [t[:2] for t in A[0][2]]
+    else:
+        assert torch.equal(B[0][0][:, :, :mo], A[0][0])
+
+
 def test_gpu_synth_matches_oracle_synth():
     M, cp, N, nac, pid, qam = 128, 16, 4, 3, 5, 64
     S = Synthesizer(SynthParams(M=M, cp_len=cp, num_streams=N, num_access_codes=nac, pid=pid,
