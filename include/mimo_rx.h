@@ -328,7 +328,8 @@ int mimo_rx_sic_mse(mimo_rx *h, float *mse, uint32_t n_frames);
  *
  * nu_sic is the error power of stage k's estimate when the earlier decisions were right
  * (perfect cancellation): error propagation is not in the weight, so the LLRs of the later
- * stages are optimistic where an earlier stage decided wrongly. */
+ * stages are optimistic where an earlier stage decided wrongly. mimo_rx_sic_soft_fb below
+ * carries that into the weight: call it for calibrated LLRs. */
 typedef struct mimo_sic_soft {
   const void *d_sym;      /* the last batch's d_out_sym */
   void *d_llr;            /* [d_sym's rows][M_occ][2b] int8 or float; required */
@@ -346,6 +347,35 @@ typedef struct mimo_sic_soft {
  * MIMO_ERR_STATE before any batch; MIMO_DET_SISO, and MIMO_DET_ZF2 at N != 2, return
  * MIMO_ERR_UNSUPPORTED. */
 int mimo_rx_sic_soft(mimo_rx *h, const mimo_sic_soft *a, void *hip_stream);
+
+/* ---------------- soft-feedback SIC: expected-symbol cancellation, calibrated LLRs ----
+ * mimo_rx_sic_soft with two changes: a stage cancels the posterior mean of the earlier symbols
+ * instead of their hard decisions, and its weight carries their posterior variance. The same
+ * argument struct, conditions, errors and side-effect rules as mimo_rx_sic_soft; the order pi,
+ * T, C and nu_sic are steps 1-5 above, unchanged; mimo_rx_sic_detect stays the hard detector.
+ *
+ * l_m the L fp32 levels of qam_point. Per symbol, stage k = 0..N-1:
+ *   z_k   = sum_u T[k][u] y_u - sum_{i<k} C[k][i] sbar_i
+ *   nu_k  = nu_sic[pi_k] + sum_{i<k} |C[k][i]|^2 v_i
+ *   idx_k = the decode's own slicer of z_k
+ *   LLR_i = llr_scale delta_i(z_k) / max(nu_k, 1e-30)     (delta, formats, NaN -> 0 as above)
+ *   for x = Re z_k and x = Im z_k: p_m ~ exp(-(x - l_m)^2 / max(nu_k, 1e-30)) over the L levels
+ *     (the complex error power nu_k is nu_k / 2 per real dimension), normalised to sum 1;
+ *     mean = sum_m p_m l_m, variance = max(sum_m p_m l_m^2 - mean^2, 0)
+ *   sbar_k = (mean of Re) + j (mean of Im), v_k = (variance of Re) + (variance of Im)
+ * (the last stage needs neither). The posterior is evaluated relative to the slicer's level l_c
+ * of x: with t = x - l_c and o_m = l_m - l_c, w_m = exp(-max(o_m (o_m - 2 t), 0) / nu_k),
+ * mean = l_c + sum w o / sum w, variance = sum w o^2 / sum w - (sum w o / sum w)^2. That is the
+ * same posterior (l_c is the nearest level, so the exponent is >= 0 but for the slicer's
+ * rounding at a boundary); no weight exceeds 1 and the slicer's own is 1, so it neither
+ * overflows nor gives 0/0 for any z or nu. As nu_k -> 0, sbar_k is the hard point and v_k = 0.
+ *
+ * Stage 0 cancels nothing: its z, idx and LLRs are mimo_rx_sic_soft's bit for bit, and at N = 1
+ * the whole call is. Failed-solve carriers (all-zero tables, LLRs 0), erased rows (z = 0, idx =
+ * 0, LLRs 0) and a NaN y (every stage's z is NaN) are as in mimo_rx_sic_soft. Instances exist
+ * for N = 1, 2, 4, 8; N = 3 returns MIMO_ERR_UNSUPPORTED. The weight is calibrated for the
+ * linear filter at hand: T and C are not recomputed from the residual variances. */
+int mimo_rx_sic_soft_fb(mimo_rx *h, const mimo_sic_soft *a, void *hip_stream);
 
 /* stage timing with HIP events on the handle's launch stream (for the roofline line).
  * stages: 0 S&C, 1 plateau, 2 search, 3 LS, 4 weights, 5 decode, 6 EVM reduce; an sc16 batch

@@ -118,6 +118,7 @@ SIGNATURES = {
     "mimo_rx_batch_mse": (C.c_int, [_vp, _vp, _u32]),
     "mimo_rx_sic_detect": (C.c_int, [_vp, _P(SicDetect), _vp]),
     "mimo_rx_sic_soft": (C.c_int, [_vp, _P(SicSoft), _vp]),
+    "mimo_rx_sic_soft_fb": (C.c_int, [_vp, _P(SicSoft), _vp]),
     "mimo_rx_sic_order": (C.c_int, [_vp, _vp, _u32]),
     "mimo_rx_sic_mse": (C.c_int, [_vp, _vp, _u32]),
     "mimo_rx_set_timing": (C.c_int, [_vp, C.c_int]),

@@ -1,6 +1,7 @@
 // rub_mimo_amd/csrc/engine_sic.cpp -- ordered MMSE-SIC detection over the last batch
-// (sic_kernels.hip): mimo_rx_sic_detect, mimo_rx_sic_soft (the same pass with per-bit LLRs) and
-// the getters of the detection order and post-SIC MSE. Opt-in passes like the soft output: the
+// (sic_kernels.hip): mimo_rx_sic_detect, mimo_rx_sic_soft (the same pass with per-bit LLRs),
+// mimo_rx_sic_soft_fb (that pass cancelling expected symbols) and the getters of the detection
+// order and post-SIC MSE. Opt-in passes like the soft output: the
 // batch itself launches nothing for them.
 #include "engine_internal.hpp"
 
@@ -54,9 +55,10 @@ static int sic_pass_check(const mimo_rx *h, const void *d_sym, const void *d_out
   return MIMO_OK;
 }
 
-// both passes after their own argument checks: the shared checks, the tables, the symbol pass.
-// A null a->d_llr is the hard output (format and llr_scale are not looked at then).
-static int sic_pass(mimo_rx *h, const mimo_sic_soft *a, void *hip_stream) {
+// every pass after its own argument checks: the shared checks, the tables, the symbol pass.
+// A null a->d_llr is the hard output (format and llr_scale are not looked at then); feedback
+// is the soft output with expected-symbol cancellation.
+static int sic_pass(mimo_rx *h, const mimo_sic_soft *a, bool feedback, void *hip_stream) {
   int rc = sic_pass_check(h, a->d_sym, a->d_out_sym, a->n_frames, a->max_out_syms, a->out_layout);
   if (rc) return rc;
   hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
@@ -78,6 +80,7 @@ static int sic_pass(mimo_rx *h, const mimo_sic_soft *a, void *hip_stream) {
     k.llr_scale = a->llr_scale;
     k.f32 = a->format == MIMO_LLR_F32;
     k.bits = h->qam.b;
+    k.feedback = feedback ? 1 : 0;
   }
   if (!launch_sic_pass(k, a->n_frames, s))
     return fail(MIMO_ERR_UNSUPPORTED,
@@ -99,10 +102,11 @@ int mimo_rx_sic_detect(mimo_rx *h, const mimo_sic_detect *a, void *hip_stream) {
   mimo_sic_soft q{};     // d_llr null: hard output
   q.d_sym = a->d_sym; q.d_out_sym = a->d_out_sym; q.d_out_idx = a->d_out_idx;
   q.n_frames = a->n_frames; q.max_out_syms = a->max_out_syms; q.out_layout = a->out_layout;
-  return sic_pass(h, &q, hip_stream);
+  return sic_pass(h, &q, false, hip_stream);
 }
 
-int mimo_rx_sic_soft(mimo_rx *h, const mimo_sic_soft *a, void *hip_stream) {
+// the argument checks mimo_rx_sic_soft and mimo_rx_sic_soft_fb share
+static int sic_soft_args(const mimo_rx *h, const mimo_sic_soft *a) {
   if (!h || !a || !a->d_sym || !a->d_llr) return fail(MIMO_ERR_ARG, "null argument");
   if (((uintptr_t)a->d_sym & 15u) || ((uintptr_t)a->d_llr & 15u) ||
       ((uintptr_t)a->d_out_sym & 15u) || ((uintptr_t)a->d_out_idx & 15u))
@@ -111,7 +115,17 @@ int mimo_rx_sic_soft(mimo_rx *h, const mimo_sic_soft *a, void *hip_stream) {
     return fail(MIMO_ERR_ARG, "llr_scale must be finite and positive");
   if (a->format != MIMO_LLR_I8 && a->format != MIMO_LLR_F32)
     return fail(MIMO_ERR_ARG, "mimo_sic_soft.format must be MIMO_LLR_I8 or _F32");
-  return sic_pass(h, a, hip_stream);
+  return MIMO_OK;
+}
+
+int mimo_rx_sic_soft(mimo_rx *h, const mimo_sic_soft *a, void *hip_stream) {
+  const int rc = sic_soft_args(h, a);
+  return rc ? rc : sic_pass(h, a, false, hip_stream);
+}
+
+int mimo_rx_sic_soft_fb(mimo_rx *h, const mimo_sic_soft *a, void *hip_stream) {
+  const int rc = sic_soft_args(h, a);
+  return rc ? rc : sic_pass(h, a, true, hip_stream);
 }
 
 // the getters' common part: the tables of every slot of the last batch, finished

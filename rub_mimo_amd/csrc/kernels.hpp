@@ -389,7 +389,8 @@ bool launch_sic_tables(const SicTableArgs &a, uint32_t n_frames, hipStream_t s);
 
 // the symbol pass: hard output (mimo_rx_sic_detect: llr null and bits 0; nu, ok, llr_scale and
 // f32 are not read) or the same pass with the max-log LLRs of every stage's z
-// (mimo_rx_sic_soft: out_sym and out_idx may both be null there)
+// (mimo_rx_sic_soft: out_sym and out_idx may both be null there), every stage cancelling its
+// hard decision or, with `feedback`, its expected symbol (mimo_rx_sic_soft_fb)
 struct SicPassArgs {
   const float2 *sym;               // the batch's d_out_sym
   float2 *out_sym;                 // z, same layout, or null
@@ -406,6 +407,8 @@ struct SicPassArgs {
   float llr_scale;
   int f32;                         // MIMO_LLR_F32
   uint32_t bits;                   // per dimension (1..4), 0 for hard output
+  int feedback;                    // mimo_rx_sic_soft_fb: cancel expected symbols (bits > 0;
+                                   // the launcher alone reads it, the kernels are instances)
 };
 // false when (N, bits) has no instance or the batch shape does not fit (nothing launched)
 bool launch_sic_pass(const SicPassArgs &a, uint32_t n_frames, hipStream_t s);

@@ -1,7 +1,8 @@
 // rub_mimo_amd/csrc/sic_kernels.hip -- ordered MMSE-SIC detection on gfx950: the per-carrier
 // detection order and tables of a batch's frames, and the pass that applies them to the batch's
 // equalised symbols (mimo_rx_sic_detect, DESIGN.md "SIC detection"), alone or with the
-// max-log LLRs of every stage (mimo_rx_sic_soft, DESIGN.md "Soft-output SIC").
+// max-log LLRs of every stage (mimo_rx_sic_soft, DESIGN.md "Soft-output SIC"), and that soft
+// output with expected-symbol cancellation (mimo_rx_sic_soft_fb, DESIGN.md "Soft-feedback SIC").
 //
 // No reference counterpart: framing.cc's detectors are linear. A separate, opt-in pass over the
 // decode's d_out_sym; nothing here is launched by the batch itself.
@@ -250,6 +251,15 @@ bool launch_sic_tables(const SicTableArgs &a, uint32_t n_frames, hipStream_t s) 
 // either end of a row whose address or length is no multiple of 16 leave in narrower pieces.
 // The image sets the symbols per iteration: sic_sc<N>() halved until it fits kSicLlrImg.
 //
+// Soft feedback (FB, a form of B > 0 for N = 2, 4, 8: mimo_rx_sic_soft_fb) changes phase 2
+// alone, behind if constexpr (FB), so that the other instances compile to what they compiled to
+// without it: after the slicer, stage k < N - 1 replaces its point sh[k] by the posterior mean
+// of its symbol and keeps the posterior variance (sic_soft_symbol), and stage k >= 1 weights its
+// LLRs by llr_scale / max(nu_k, 1e-30) with nu_k = nu_sic + sum_{i<k} |C[k][i]|^2 var[i], one
+// division per stage and symbol (stage 0 keeps the precomputed weight and is the soft output's
+// bit for bit). Loads, stores, both images and both drains are the soft output's; the int8
+// instances take half its symbols per iteration (SC in the kernel says why).
+//
 // The four phases (table prologue, one symbol's stages, LLR drain, index drain) are marked in
 // the body, not split into functions. Each was tried as a MIMO_DEV function on a per-lane
 // struct, one at a time: the symbol phase changed occupancy or scratch of 10 of the 45
@@ -325,9 +335,57 @@ MIMO_DEV void sic_llr_put(uint8_t *p, const float *v) {
   }
 }
 
-template <int N, int B, bool F32>
+// Soft feedback (FB, mimo_rx_sic_soft_fb): the posterior mean and variance of one stage's symbol
+// given its z and the stage's error power nu, per dimension p_m ~ exp(-(x - l_m)^2 / nu) over
+// the L levels. On entry *pt is the slicer's point l_c of z, on return the mean; *var the sum of
+// both dimensions' variances. The exponents are taken relative to l_c: with t = x - l_c and
+// o_m = l_m - l_c, (x - l_m)^2 - (x - l_c)^2 = o_m (o_m - 2 t) = e_m >= 0 up to the slicer's
+// rounding at a boundary (floored at 0), so every weight is at most 1, the slicer's own is
+// exactly 1, and the sums can neither overflow nor vanish however far z lies outside the grid
+// or however small nu is. Both dimensions run side by side as one packed value; the L levels
+// are a loop over three running sums (sum w, sum w o, sum w o^2), not L live weights. exp is
+// one v_exp_f32 on e_m (-log2 e / nu): its arguments are <= 0, so a result below the normal
+// range may flush to 0, as a term that small vanishes in the sums anyway. The two reciprocals
+// are v_rcp_f32 (1 ulp).
+template <int B>
+MIMO_DEV void sic_soft_symbol(v2f z, float nu, float scale, v2f *pt, float *var) {
+  constexpr int L = 1 << B;
+  const float g = -1.44269504f * __builtin_amdgcn_rcpf(fmaxf(nu, 1e-30f));
+  const v2f lc = *pt;
+  v2f t2 = z - lc;
+  t2 = t2 + t2;
+  v2f sw = v2f{0.0f, 0.0f}, swo = v2f{0.0f, 0.0f}, swoo = v2f{0.0f, 0.0f};
+#pragma unroll
+  for (int m = 0; m < L; m++) {
+    const float lm = (float)(2 * m - (L - 1)) * scale;
+    const v2f o = v2f{lm, lm} - lc;
+    const v2f e = o * (o - t2);
+    v2f w;
+    w.x = __builtin_amdgcn_exp2f(fmaxf(e.x, 0.0f) * g);
+    w.y = __builtin_amdgcn_exp2f(fmaxf(e.y, 0.0f) * g);
+    const v2f wo = w * o;
+    sw = sw + w;
+    swo = swo + wo;
+    swoo = __builtin_elementwise_fma(wo, o, swoo);
+  }
+  v2f r;
+  r.x = __builtin_amdgcn_rcpf(sw.x);
+  r.y = __builtin_amdgcn_rcpf(sw.y);
+  const v2f mo = swo * r;
+  const v2f vv = swoo * r - mo * mo;
+  *pt = lc + mo;
+  *var = fmaxf(vv.x, 0.0f) + fmaxf(vv.y, 0.0f);
+}
+
+template <int N, int B, bool F32, bool FB = false>
 __global__ __launch_bounds__(kSicT) void sic_pass_kernel(SicPassArgs a) {
-  constexpr int SC = B > 0 ? sic_soft_sc<N, B, F32>() : sic_sc<N>();
+  static_assert(!FB || (B > 0 && N > 1), "soft feedback is a form of the soft output at N > 1");
+  // FB int8 takes half the symbols per iteration: with the full count 64-QAM at N = 4 needs
+  // 256 VGPRs + 20 AGPRs and falls to one wave per SIMD (6.95 ms at C3 x 64 against 4.59 ms
+  // with half); FB fp32 fits two waves with the full count and is slower with half (4.98 ms
+  // against 5.65 ms)
+  constexpr int SC0 = B > 0 ? sic_soft_sc<N, B, F32>() : sic_sc<N>();
+  constexpr int SC = (FB && !F32 && SC0 > 1) ? SC0 / 2 : SC0;
   constexpr int NC = (int)sic_c_rows(N);
   constexpr int SLOTS = kSicT / 4 + 1;   // dwords a row's kSicT index bytes can touch
   constexpr int BPS = sic_llr_bps<B, F32>();
@@ -361,6 +419,7 @@ __global__ __launch_bounds__(kSicT) void sic_pass_kernel(SicPassArgs a) {
   uint32_t ord[N];       // stage k's stream as its element offset pi_k r_ts M_occ, and pi_k
   uint32_t pis[N];
   float wk[N];           // B > 0: stage k's weight llr_scale / max(nu_sic of pi_k, 1e-30)
+  float nus[FB ? N : 1]; // FB: nu_sic of pi_k (the weight of a stage k > 0 is per symbol there)
   C[0] = make_float2(0.0f, 0.0f);
   const bool work = lane && s_lo < n_out;
   // a failed solve (or an unsynced slot): NaN in place of z makes every LLR exactly 0
@@ -372,8 +431,12 @@ __global__ __launch_bounds__(kSicT) void sic_pass_kernel(SicPassArgs a) {
     pis[k] = work ? min((uint32_t)a.order[((uint64_t)f * mo + j) * N + k], (uint32_t)(N - 1))
                   : (uint32_t)k;
     ord[k] = pis[k] * r_ts * a.M_occ;
-    if constexpr (B > 0)
+    if constexpr (FB) {
+      nus[k] = work ? a.nu[((uint64_t)f * N + pis[k]) * mo + j] : 0.0f;
+      if (k == 0) wk[0] = work ? a.llr_scale / fmaxf(nus[0], 1e-30f) : 0.0f;
+    } else if constexpr (B > 0) {
       wk[k] = work ? a.llr_scale / fmaxf(a.nu[((uint64_t)f * N + pis[k]) * mo + j], 1e-30f) : 0.0f;
+    }
 #pragma unroll
     for (int u = 0; u < N; u++)
       T[k][u] = work ? a.T[((uint64_t)f * N * N + k * N + u) * mo + j] : make_float2(0.0f, 0.0f);
@@ -409,6 +472,7 @@ __global__ __launch_bounds__(kSicT) void sic_pass_kernel(SicPassArgs a) {
         // stage k's z and index go straight to the row of its stream pi_k: the order changes
         // slowly along the carriers, so a wave's store still covers whole runs of a row
         v2f yr[N], sh[N], shr[N];
+        float var[FB ? N : 1];          // FB: the variance of the symbol stage k cancels
 #pragma unroll
         for (int u = 0; u < N; u++) yr[u] = sic_rot(y[q][u]);
 #pragma unroll
@@ -419,14 +483,27 @@ __global__ __launch_bounds__(kSicT) void sic_pass_kernel(SicPassArgs a) {
 #pragma unroll
           for (int i = 0; i < k; i++) z = sic_mac(z, C[k * (k - 1) / 2 + i], sh[i], shr[i]);
           const uint32_t idx = sic_slice(z, a.qam, &sh[k]);
+          float w = wk[FB ? 0 : k];
+          if constexpr (FB) {
+            // the error power with the cancelled symbols' variances in it, the weight from it,
+            // and the expected symbol in place of the point (the last stage cancels nothing)
+            float nuk = nus[k];
+#pragma unroll
+            for (int i = 0; i < k; i++) {
+              const float2 c = C[k * (k - 1) / 2 + i];
+              nuk = __builtin_fmaf(__builtin_fmaf(c.x, c.x, c.y * c.y), var[i], nuk);
+            }
+            if (k > 0) w = a.llr_scale / fmaxf(nuk, 1e-30f);
+            if (k < N - 1) sic_soft_symbol<B>(z, nuk, a.qam.scale, &sh[k], &var[k]);
+          }
           shr[k] = sic_rot(sh[k]);
           if (a.out_sym)
             __builtin_nontemporal_store(z, reinterpret_cast<v2f *>(a.out_sym + sbase + ord[k]));
           img[(q * N + pis[k]) * kSicT + tid] = (uint8_t)idx;
           if constexpr (B > 0) {
             float lv[2 * B];
-            llr_dim<B>(good ? z.x : nanv, a.qam.scale, wk[k], lv);
-            llr_dim<B>(good ? z.y : nanv, a.qam.scale, wk[k], lv + B);
+            llr_dim<B>(good ? z.x : nanv, a.qam.scale, w, lv);
+            llr_dim<B>(good ? z.y : nanv, a.qam.scale, w, lv + B);
             sic_llr_put<B, F32>(limg + (q * N + pis[k]) * RS + ((lsym + ord[k] * BPS) & 15u) +
                                     tid * BPS, lv);
           }
@@ -500,24 +577,26 @@ __global__ __launch_bounds__(kSicT) void sic_pass_kernel(SicPassArgs a) {
   }
 }
 
-template <int N, int B, bool F32>
+template <int N, int B, bool F32, bool FB>
 static void sic_pass_launch(const SicPassArgs &a, uint32_t nf, hipStream_t s) {
   const dim3 grid((a.M_occ + kSicT - 1) / kSicT, (a.max_out + kSicSB - 1) / kSicSB, nf);
-  hipLaunchKernelGGL((sic_pass_kernel<N, B, F32>), grid, dim3(kSicT), 0, s, a);
+  hipLaunchKernelGGL((sic_pass_kernel<N, B, F32, FB>), grid, dim3(kSicT), 0, s, a);
 }
 
-template <int N>
+template <int N, bool FB>
 static bool sic_pass_bits(const SicPassArgs &a, uint32_t nf, hipStream_t s) {
   switch (a.bits * 2 + (a.f32 ? 1 : 0)) {
-    case 0: sic_pass_launch<N, 0, false>(a, nf, s); return true;
-    case 2: sic_pass_launch<N, 1, false>(a, nf, s); return true;
-    case 3: sic_pass_launch<N, 1, true>(a, nf, s); return true;
-    case 4: sic_pass_launch<N, 2, false>(a, nf, s); return true;
-    case 5: sic_pass_launch<N, 2, true>(a, nf, s); return true;
-    case 6: sic_pass_launch<N, 3, false>(a, nf, s); return true;
-    case 7: sic_pass_launch<N, 3, true>(a, nf, s); return true;
-    case 8: sic_pass_launch<N, 4, false>(a, nf, s); return true;
-    case 9: sic_pass_launch<N, 4, true>(a, nf, s); return true;
+    case 0:
+      if constexpr (FB) return false;
+      else { sic_pass_launch<N, 0, false, false>(a, nf, s); return true; }
+    case 2: sic_pass_launch<N, 1, false, FB>(a, nf, s); return true;
+    case 3: sic_pass_launch<N, 1, true, FB>(a, nf, s); return true;
+    case 4: sic_pass_launch<N, 2, false, FB>(a, nf, s); return true;
+    case 5: sic_pass_launch<N, 2, true, FB>(a, nf, s); return true;
+    case 6: sic_pass_launch<N, 3, false, FB>(a, nf, s); return true;
+    case 7: sic_pass_launch<N, 3, true, FB>(a, nf, s); return true;
+    case 8: sic_pass_launch<N, 4, false, FB>(a, nf, s); return true;
+    case 9: sic_pass_launch<N, 4, true, FB>(a, nf, s); return true;
     default: return false;
   }
 }
@@ -527,12 +606,23 @@ bool launch_sic_pass(const SicPassArgs &a, uint32_t n_frames, hipStream_t s) {
   if (n_frames == 0 || a.max_out == 0 || a.M_occ == 0) return true;
   if (n_frames > 65535u || (a.max_out + kSicSB - 1) / kSicSB > 65535u) return false;
   if ((uint64_t)a.N * a.max_out * a.M_occ >= 0xFFFFFFFFull) return false;
+  if (a.feedback && a.bits == 0) return false;
+  // soft feedback: N = 1 has nothing to cancel and is the soft output's instance; N = 3 (no
+  // receiver takes it) has none
+  if (a.feedback && a.N > 1) {
+    switch (a.N) {
+      case 2: return sic_pass_bits<2, true>(a, n_frames, s);
+      case 4: return sic_pass_bits<4, true>(a, n_frames, s);
+      case 8: return sic_pass_bits<8, true>(a, n_frames, s);
+      default: return false;
+    }
+  }
   switch (a.N) {
-    case 1: return sic_pass_bits<1>(a, n_frames, s);
-    case 2: return sic_pass_bits<2>(a, n_frames, s);
-    case 3: return sic_pass_bits<3>(a, n_frames, s);
-    case 4: return sic_pass_bits<4>(a, n_frames, s);
-    case 8: return sic_pass_bits<8>(a, n_frames, s);
+    case 1: return sic_pass_bits<1, false>(a, n_frames, s);
+    case 2: return sic_pass_bits<2, false>(a, n_frames, s);
+    case 3: return sic_pass_bits<3, false>(a, n_frames, s);
+    case 4: return sic_pass_bits<4, false>(a, n_frames, s);
+    case 8: return sic_pass_bits<8, false>(a, n_frames, s);
     default: return false;
   }
 }

@@ -317,6 +317,20 @@ class Receiver:
                          llr_scale)
         check(lib().mimo_rx_sic_soft(self._h, C.byref(a), stream), "sic_soft")
 
+    def sic_soft_fb(self, sym, llr, out_sym=None, out_idx=None, n_frames=None, max_out=None,
+                    out_layout=0, fmt=_lib.LLR_I8, llr_scale=1.0, stream=None):
+        """Soft-feedback SIC of the last batch's equalised symbols (mimo_rx_sic_soft_fb):
+        sic_soft with every stage cancelling the expected symbols of the earlier stages
+        instead of their hard decisions, and weighting its LLRs by llr_scale / nu_k with the
+        cancelled symbols' variances in nu_k (sic.sic_apply_soft), so that the LLRs stay
+        calibrated where decisions are wrong. Arguments, outputs and conditions as sic_soft;
+        stage 0 (and all of N = 1) is sic_soft's output bit for bit."""
+        a = _lib.SicSoft(_ptr(sym), _ptr(llr), _ptr(out_sym), _ptr(out_idx),
+                         self._last if n_frames is None else n_frames,
+                         self.params.pid_max if max_out is None else max_out, out_layout, fmt,
+                         llr_scale)
+        check(lib().mimo_rx_sic_soft_fb(self._h, C.byref(a), stream), "sic_soft_fb")
+
     def sic_order(self, n_frames=None):
         """Detection order [n_frames][M_occ][N] (uint8 stream indices, first detected first) of
         the last batch (mimo_rx_sic_order); zero rows for slots that did not sync."""

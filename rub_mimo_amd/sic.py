@@ -23,6 +23,22 @@ minus min over the levels with bit i = 0, bit 0 the index's most significant bit
 sign is the matching bit of the stage's index. A NaN z gives 0, and so does every carrier whose
 solve failed: that is not the good carrier with nu_sic = 0 because s2 = 0, which takes the
 floor. nu_sic assumes perfect cancellation: error propagation is not in the weight.
+
+Soft feedback (mimo_rx_sic_soft_fb; soft_symbol, sic_apply_soft): the order, T, C and nu_sic
+above, but a stage cancels the expected symbols of the earlier stages and carries their
+variances in its weight. With l_m the levels (qam_levels), per symbol and stage k:
+  z_k = sum_u T[k][u] y_u - sum_{i<k} C[k][i] sbar_i
+  nu_k = nu_sic[pi_k] + sum_{i<k} |C[k][i]|^2 v_i
+  idx_k = slice(z_k);  LLR_i = llr_scale delta_i(z_k) / max(nu_k, 1e-30)
+  per dimension x of z_k: p_m ~ exp(-(x - l_m)^2 / max(nu_k, 1e-30)) (the complex error power
+  nu_k is nu_k / 2 per real dimension), mean = sum p_m l_m, variance = sum p_m l_m^2 - mean^2
+  floored at 0;  sbar_k = mean(Re) + j mean(Im),  v_k = variance(Re) + variance(Im)
+The posterior is evaluated relative to the slicer's level l_c of x: t = x - l_c, o_m = l_m - l_c,
+w_m = exp(-max(o_m (o_m - 2 t), 0) / nu_k), mean = l_c + sum w o / sum w, variance =
+sum w o^2 / sum w - (sum w o / sum w)^2: the same posterior (l_c is the nearest level, so the
+floor only acts on the slicer's rounding at a boundary), with no weight above 1 and the
+slicer's own equal to 1, so that nothing overflows or becomes 0/0 for any z or nu. Stage 0, and
+all of N = 1, is the soft output above; nu -> 0 gives the hard point and v = 0.
 """
 from __future__ import annotations
 
@@ -216,3 +232,80 @@ def sic_llr(z, nu_sic, qam_order, llr_scale=1.0, failed=None):
     if failed is not None:
         out = np.where(np.broadcast_to(np.asarray(failed, bool), shape)[..., None], 0.0, out)
     return out
+
+
+def soft_symbol(z, nu, qam_order):
+    """Posterior mean and variance of the symbol behind z = s + e, e ~ CN(0, nu), s uniform on
+    the constellation: per dimension p_m ~ exp(-(x - l_m)^2 / max(nu, 1e-30)), evaluated in the
+    offset form of the module docstring around the slicer's level (qam_demap_f32). z complex, nu
+    broadcast against it. Returns (sbar complex128, v float64 = Re variance + Im variance)."""
+    z = np.asarray(z, np.complex128)
+    lv = qam_levels(qam_order)
+    nu = np.maximum(np.broadcast_to(np.asarray(nu, np.float64), z.shape), MSE_FLOOR)
+    pt = qam_points(qam_demap_f32(z, qam_order), qam_order)
+
+    def dim(x, lc):
+        o = lv - lc[..., None]                                   # [..., L]
+        with np.errstate(invalid="ignore", over="ignore"):
+            e = np.fmax(o * (o - 2.0 * (x - lc)[..., None]), 0.0)
+            w = np.exp(-e / nu[..., None])
+        sw = w.sum(axis=-1)
+        m = (w * o).sum(axis=-1) / sw
+        return lc + m, np.maximum((w * o * o).sum(axis=-1) / sw - m * m, 0.0)
+
+    mr, vr = dim(z.real, pt.real)
+    mi, vi = dim(z.imag, pt.imag)
+    return mr + 1j * mi, vr + vi
+
+
+def sic_apply_soft(y, order, T, C, nu_sic, qam_order, fed_z=None, with_mag=False):
+    """The symbol pass with soft feedback. y [N][n_sym][J] the linear decode's output by
+    stream; order, T, C, nu_sic ([J][N] by stream) as sic_tables returns them. Returns
+    (z [N][n_sym][J] complex128, idx [N][n_sym][J] uint8, nu [N][n_sym][J] float64 the error
+    power nu_k that weights the stage's LLRs), all by stream. With `fed_z` ([N][n_sym][J] by
+    stream) stage k's sbar_i and v_i are computed from the given earlier z, with the model's own
+    nu_i, instead of from its own z (teacher forcing). with_mag adds the magnitude sum
+    sum_u |T[k][u]| |y_u| + sum_{i<k} |C[k][i]| |sbar_i| of each z, by stream."""
+    y = np.asarray(y, np.complex128)
+    N, n, J = y.shape
+    order = np.asarray(order, np.int64).reshape(J, N)
+    T = np.asarray(T, np.complex128)
+    C = np.asarray(C, np.complex128)
+    nu_sic = np.asarray(nu_sic, np.float64).reshape(J, N)
+    z = np.zeros((N, n, J), np.complex128)
+    idx = np.zeros((N, n, J), np.uint8)
+    nu = np.zeros((N, n, J), np.float64)
+    mag = np.zeros((N, n, J), np.float64)
+    ar = np.arange(J)
+    sbar, var = [], []
+    ay = np.abs(y)
+    for k in range(N):
+        pi = order[:, k]
+        zk = np.einsum("ju,unj->nj", T[:, k, :], y)
+        mk = np.einsum("ju,unj->nj", np.abs(T[:, k, :]), ay)
+        nk = np.broadcast_to(nu_sic[ar, pi][None, :], (n, J)).copy()
+        for i in range(k):
+            zk = zk - C[:, k, i][None, :] * sbar[i]
+            mk = mk + np.abs(C[:, k, i])[None, :] * np.abs(sbar[i])
+            nk = nk + (np.abs(C[:, k, i]) ** 2)[None, :] * var[i]
+        z[pi, :, ar] = zk.T
+        idx[pi, :, ar] = qam_demap_f32(zk, qam_order).T
+        nu[pi, :, ar] = nk.T
+        mag[pi, :, ar] = mk.T
+        src = zk if fed_z is None else np.asarray(fed_z, np.complex128)[pi, :, ar].T
+        sb, vv = soft_symbol(src, nk, qam_order)
+        sbar.append(sb)
+        var.append(vv)
+    return (z, idx, nu, mag) if with_mag else (z, idx, nu)
+
+
+def llr_gmi(llr, sent_idx, qam_order):
+    """Generalised mutual information per bit of LLRs [..., 2b] (positive = bit 0) against the
+    transmitted indices sent_idx [...]: 1 - E log2(1 + exp(-LLR)) over the bits sent as 0 and
+    1 - E log2(1 + exp(+LLR)) over those sent as 1, bit i counted from the index's most
+    significant bit. The rate a bit-interleaved decoder fed these LLRs could reach."""
+    nb = 2 * qam_bits(qam_order)
+    llr = np.asarray(llr, np.float64)
+    sent = np.asarray(sent_idx).astype(np.int64)
+    bits = (sent[..., None] >> (nb - 1 - np.arange(nb))) & 1
+    return 1.0 - float(np.mean(np.logaddexp(0.0, np.where(bits == 1, llr, -llr)))) / np.log(2.0)
