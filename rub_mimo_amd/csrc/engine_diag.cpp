@@ -2,7 +2,7 @@
 // diagnostic reports they turn on (device-to-host copies, a stream synchronisation and
 // fprintf to stderr: none of it is on the hot path). The stage drivers call each in one line;
 // tools/ scripts parse the printed text. (RMIMO_SEARCH_FORM, RMIMO_SEARCH_WAVE and the S&C
-// kernels' own RMIMO_SC_DIAG are read in est_kernels.hip and sync_kernels.hip.)
+// kernels' own RMIMO_SC_DIAG are read in est_kernels.hip and sc_item_kernels.hip.)
 #include "engine_internal.hpp"
 
 namespace mimo {

@@ -1,8 +1,21 @@
-// rub_mimo_amd/csrc/est_kernels.hip -- channel estimation stages on gfx950:
-//   codes_kernel   : S0/S1 time-domain codes and their zero-padded F-point spectra
-//   search_kernel  : access-code timing search (framing.cc:702-744)
-//   ls_kernel      : LS channel estimate + training-residual noise variance (framing.cc:797-824)
-//   weights_kernel : per-subcarrier detector weights (framing.cc:826-831 -> 1344-1367)
+// rub_mimo_amd/csrc/est_kernels.hip -- access-code timing search (framing.cc:702-744) on
+// gfx950, and the LS estimate that runs on the same transforms:
+//   search_kernel         : one (frame, rx, slot, lag chunk) per workgroup, transforms in LDS
+//   search_reg_kernel     : its register-resident form (F >= 1024)
+//   search_ls_wave_kernel : two slots per transform with each slot's LS term fused in, wave-local
+//                           1024-point sub-transforms (the default, F >= 1024)
+//   search_ls_kernel      : the same with workgroup-wide exchanges (RMIMO_SEARCH_FORM=block)
+//   ls_window_kernel      : LS estimate straight from the code windows at the search's keys
+//                           (framing.cc:797-824; the default LS form)
+// The code spectra come from codes_kernels.hip; the stored LS terms are summed in ls_kernels.hip.
+//
+// Why these five share a translation unit: they are built from the same register-plan helpers
+// (fft_reg.hpp: RegPlan<10, 16> in search_reg_kernel and the wave-local sub-transforms,
+// RegPlan<LOG2M, 8> in the fused LS transform and ls_window_kernel). hipcc propagates constants
+// and value ranges into a helper instance from all of its callers in the unit before it inlines
+// it, so the code of one kernel depends on which of the others are compiled with it:
+// search_reg_kernel<10>, search_ls_wave_kernel<11, 9> and ls_window_kernel<9 | 12> change when
+// they are compiled apart (profiles/r13/asm_identity.txt).
 //
 // Search. The reference takes, for every lag i in [0, SL) and every (rx, slot), an M-point
 // FFT of the window at i and the metric |sum_k X_k conj(S_k)|^2 / M^2: SL*N*(N*nac+1) FFTs
@@ -12,60 +25,15 @@
 // F-sample window segment, multiply by conj(FFT_F(zero-padded code)), IFFT_F; lags
 // [0, F-M] are exact linear correlations. First-maximum semantics (strict '>', initial 0,
 // framing.cc:718, 735) are kept by packing (value bits, ~index) into one 64-bit atomicMax.
+#include <cstdlib>
 #include <cstring>
 
+#include "est_common.hpp"
 #include "fft.hpp"
 #include "fft_reg.hpp"
 #include "kernels.hpp"
 
 namespace mimo {
-
-constexpr int kEstT = 256;
-
-// ------------------------------------------------------------------------------------
-template <int LOG2M, int LOG2F>
-__global__ __launch_bounds__(kEstT) void codes_kernel(CodesArgs a) {
-  constexpr int M = 1 << LOG2M, F = 1 << LOG2F;
-  extern __shared__ __attribute__((aligned(16))) float2 lds[];
-  float2 *buf = lds;
-  const int slot = blockIdx.x, tid = threadIdx.x;
-  // frequency-domain code on the first M entries
-  for (int i = tid; i < M; i += kEstT) {
-    float v = 0.0f;
-    if (a.p[i] != 0) {
-      if (slot == 0) {
-        if ((i & 1) == 0) v = (a.s0_bits[i] & 1) ? 1.0f : -1.0f;  // framing.cc:1077-1089
-      } else {
-        const int ac = slot - 1, c = ac / a.N, t = ac % a.N;
-        v = (a.s1_bits[((size_t)t * a.nac + c) * M + i] & 1) ? 1.0f : -1.0f;  // :1243-1248
-      }
-    }
-    buf[lds_pad(i)] = make_float2(v, 0.0f);
-  }
-  __syncthreads();
-  fft_lds<LOG2M, kEstT, 1, true>(buf, a.tw);
-  const float dn = (slot == 0) ? a.dn_s0 : a.dn_s1;
-  for (int i = tid; i < M; i += kEstT) {
-    float2 v = buf[lds_pad(i)];
-    v = make_float2(v.x * dn, v.y * dn);
-    a.code_time[(size_t)slot * M + i] = v;
-    buf[lds_pad(i)] = v;
-  }
-  if (a.codespec == nullptr) return;
-  __syncthreads();
-  // zero-pad to F (in place: move is safe because M <= F/2 and we only clear [M, F))
-  for (int i = M + tid; i < F; i += kEstT) buf[lds_pad(i)] = make_float2(0.0f, 0.0f);
-  __syncthreads();
-  fft_lds<LOG2F, kEstT, 1, false>(buf, a.tw);
-  for (int i = tid; i < F; i += kEstT) a.codespec[(size_t)slot * F + i] = buf[lds_pad(i)];
-  if constexpr (F >= 1024) {
-    // the wave-local search's order: bin B k + q at q * 1024 + k (B = F / 1024)
-    constexpr int B = F / 1024;
-    if (a.codespec_w)
-      for (int i = tid; i < F; i += kEstT)
-        a.codespec_w[(size_t)slot * F + (i % B) * 1024 + i / B] = buf[lds_pad(i)];
-  }
-}
 
 // DEBUG_LOG trace (framing.cc:675-696, 873-883, opt-in): every lag's metric of (frame, rx, slot)
 MIMO_DEV void corr_trace_put(const SearchArgs &a, uint32_t f, uint32_t r, uint32_t slot,
@@ -275,10 +243,6 @@ MIMO_DEV unsigned long long wave_max_u64(unsigned long long x) {
     x = max_u64(((unsigned long long)h[0] << 32) | l[0], ((unsigned long long)h[1] << 32) | l[1]);
   }
   return x;
-}
-
-MIMO_DEV uint32_t key_index(unsigned long long k) {
-  return k ? (0xFFFFFFFFu - (uint32_t)(k & 0xFFFFFFFFull)) : 0u;
 }
 
 // Search of two consecutive slots with the LS term of each fused in (one lag chunk per slot,
@@ -842,629 +806,6 @@ void search_ls_wave_kernel(SearchArgs a) {
   }
 }
 
-// one thread per (frame, subcarrier, rx-tx pair): the codes' X/S1 of lsq in code order, G and
-// this block's share of the residual variance (as ls_combine_kernel)
-constexpr int kLsRotCodes = 256;   // CFO code rotations tabled in LDS
-__global__ __launch_bounds__(256) void ls_combine_q_kernel(LsArgs a) {
-  __shared__ double red[4];
-  __shared__ double s_nu;
-  __shared__ double2 s_rot[kLsRotCodes];
-  const uint32_t rt = blockIdx.y, f = blockIdx.z;
-  const FrameInfo &I = a.info[f];
-  if (I.status != 0) return;
-  const uint32_t M = a.M, N = a.N;
-  const uint32_t k = blockIdx.x * 256 + threadIdx.x;
-  const uint32_t r_ = rt / N, t_ = rt % N;
-  // opt-in CFO: the residual's phase at each code's window (window-relative, about the frame's
-  // base), as the data region is derotated (cfo_kernels.hip stage 2) -- uniform over the
-  // workgroup, so tabled once per code instead of per subcarrier
-  const bool rot_tab = a.cfo_part && a.nac <= (uint32_t)kLsRotCodes;
-  if (a.cfo_part) {
-    if (threadIdx.x == 0) {
-      s_nu = cfo_stage_eps(a.cfo_part, f, 2) / (double)M;
-      if (blockIdx.x == 0 && rt == 0)   // the frame's total estimate (stage 1 + stage 2)
-      {
-        const double eps = cfo_stage_eps(a.cfo_part, f, 1) + s_nu * M;
-        const_cast<FrameInfo &>(I).cfo_eps = (float)eps;
-        const_cast<FrameInfo &>(I).cfo_E = cfo_fixed_freq(eps, M);
-      }
-    }
-    __syncthreads();
-    if (rot_tab) {
-      for (uint32_t c = threadIdx.x; c < a.nac; c += 256) {
-        const unsigned long long key = a.keys[((uint64_t)f * N + r_) * a.n_slots + 1 + c * N + t_];
-        const double w = (double)key_index(key) + 0.5 * (double)M;
-        double ph = -2.0 * s_nu * w;
-        ph -= 2.0 * rint(ph * 0.5);
-        double sn, cs;
-        sincospi(ph, &sn, &cs);
-        s_rot[c] = make_double2(cs, sn);
-      }
-      __syncthreads();
-    }
-  }
-  double nv = 0.0;
-  if (k < M) {
-    const bool occ = a.occ_index[k] >= 0;
-    const float2 *q = a.lsq + ((uint64_t)f * N * N + rt) * a.nac * M + k;
-    double sr = 0.0, si = 0.0, s2 = 0.0;
-    const double nu = a.cfo_part ? s_nu : 0.0;
-    // the codes' terms in batches of CB loads in flight (one latency per batch instead of per
-    // code), summed in code order as before
-    constexpr uint32_t CB = 8;
-    for (uint32_t c0 = 0; c0 < a.nac; c0 += CB) {
-      float2 vb[CB];
-#pragma unroll
-      for (uint32_t j = 0; j < CB; j++) {   // clamped: every load unconditional; read once
-        const v2f t = __builtin_nontemporal_load(reinterpret_cast<const v2f *>(q) + (uint64_t)min(c0 + j, a.nac - 1) * M);
-        vb[j] = make_float2(t.x, t.y);
-      }
-#pragma unroll
-      for (uint32_t j = 0; j < CB; j++) {
-        const uint32_t c = c0 + j;
-        if (c >= a.nac) break;
-        float2 v = vb[j];
-        if (a.cfo_part) {
-          double sn, cs;
-          if (rot_tab) {
-            cs = s_rot[c].x;
-            sn = s_rot[c].y;
-          } else {   // (more codes than the table holds)
-            const unsigned long long key =
-                a.keys[((uint64_t)f * N + r_) * a.n_slots + 1 + c * N + t_];
-            const double w = (double)key_index(key) + 0.5 * (double)M;
-            double ph = -2.0 * nu * w;
-            ph -= 2.0 * rint(ph * 0.5);
-            sincospi(ph, &sn, &cs);
-          }
-          v = make_float2((float)(v.x * cs - v.y * sn), (float)(v.x * sn + v.y * cs));
-        }
-        sr += (double)v.x;
-        si += (double)v.y;
-        s2 += (double)v.x * v.x + (double)v.y * v.y;
-      }
-    }
-    const uint32_t r = rt / N, t = rt % N;
-    const double bias = (a.keep_bias && r == t) ? 1.0 : 0.0;
-    a.G[(((uint64_t)f * M + k) * N + r) * N + t] =
-        occ ? make_float2((float)((bias + sr) * a.scale), (float)(si * a.scale))
-            : make_float2(0.0f, 0.0f);
-    if (occ) nv = s2 - (sr * sr + si * si) / (double)a.nac;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) nv += __shfl_xor(nv, off);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = nv;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    a.nv_part[(uint64_t)f * a.n_nvp + (uint64_t)rt * gridDim.x + blockIdx.x] =
-        red[0] + red[1] + red[2] + red[3];
-}
-
-// ------------------------------------------------------------------------------------
-// LS estimate, two stages. ls_kernel: one workgroup per (frame, rx, tx, code group) FFTs the
-// group's CB access codes as received on rx (the window at the search's corr index) and
-// writes the group's per-subcarrier sums of X/S1 (S1 = +-1, framing.cc:811) and |X/S1|^2 in
-// fp64. ls_combine_kernel: per (frame, subcarrier) the groups are summed in fixed order into
-// G = (I + sum) * dft_normalizer / nac (framing.cc:809-824, identity bias from :309-311) and
-// the training-residual variance sum |v - mean|^2 for the MMSE noise estimate.
-template <int LOG2M, int T, int CB>
-__global__ __launch_bounds__(T) void ls_kernel(LsArgs a) {
-  constexpr int M = 1 << LOG2M, PB = lds_padded_len(M), PER = M / T;
-  extern __shared__ __attribute__((aligned(16))) float2 lds[];
-  const uint32_t f = blockIdx.y;
-  const FrameInfo &I = a.info[f];
-  if (I.status != 0) return;
-  const uint32_t P = a.n_groups;
-  const uint32_t rt = blockIdx.x / P, grp = blockIdx.x % P;
-  const uint32_t r = rt / a.N, t = rt % a.N;
-  const int tid = threadIdx.x;
-  const float2 *__restrict__ x = a.iq + ((uint64_t)I.cap * a.N + r) * a.stride;
-  const int64_t L = (int64_t)a.frame_len;
-  const uint32_t c0 = grp * CB;
-  const uint32_t nb = min((uint32_t)CB, a.nac - c0);
-  // every code's window start first, then all 16-byte loads in flight together, then the LDS
-  // writes (a load -> ds_write loop waits out one memory latency per iteration)
-  constexpr int P2 = (M / 2 + T - 1) / T;        // 16-byte pairs per thread per code
-  int64_t abs0[CB];
-  bool fast[CB];
-#pragma unroll
-  for (int b = 0; b < CB; b++) {
-    abs0[b] = 0;
-    if (b < (int)nb) {
-      const uint32_t ac = (c0 + b) * a.N + t;
-      abs0[b] = I.base + key_index(a.keys[((uint64_t)f * a.N + r) * a.n_slots + 1 + ac]);
-    }
-    fast[b] = b < (int)nb && abs0[b] >= 0 && abs0[b] + M <= L && (abs0[b] & 1) == 0;
-  }
-  float4 stg[CB][P2];
-#pragma unroll
-  for (int b = 0; b < CB; b++) {
-    const float4 *x4 = reinterpret_cast<const float4 *>(x + (fast[b] ? abs0[b] : 0));
-#pragma unroll
-    for (int u = 0; u < P2; u++) {
-      const int i = tid + u * T;
-      stg[b][u] = (fast[b] && i < M / 2) ? x4[i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-  }
-#pragma unroll
-  for (int b = 0; b < CB; b++) {
-    if (fast[b]) {                   // 16-byte loads of two samples
-#pragma unroll
-      for (int u = 0; u < P2; u++) {
-        const int i = tid + u * T;
-        if (i < M / 2) *reinterpret_cast<float4 *>(lds + b * PB + lds_pad(2 * i)) = stg[b][u];
-      }
-    } else {
-      for (int i = tid; i < M; i += T) {
-        const int64_t n = abs0[b] + i;
-        lds[b * PB + lds_pad(i)] =
-            (b < (int)nb && n >= 0 && n < L) ? x[n] : make_float2(0.0f, 0.0f);
-      }
-    }
-  }
-  __syncthreads();
-  fft_lds<LOG2M, T, CB, false>(lds, a.tw);
-  double *pp = a.part + (((uint64_t)f * a.N * a.N + rt) * P + grp) * 3 * M;
-#pragma unroll
-  for (int q = 0; q < PER; q++) {
-    const int k = tid + q * T;
-    double sr = 0.0, si = 0.0, s2 = 0.0;
-    for (int b = 0; b < (int)nb; b++) {
-      const int sg = a.s1sign[((size_t)t * a.nac + c0 + b) * M + k];
-      if (sg == 0) continue;                     // null subcarrier
-      const float2 X = lds[b * PB + lds_pad(k)];
-      const float2 v = (sg > 0) ? X : cneg(X);   // X / S1
-      sr += (double)v.x;
-      si += (double)v.y;
-      s2 += (double)v.x * v.x + (double)v.y * v.y;
-    }
-    pp[k] = sr;
-    pp[M + k] = si;
-    pp[2 * M + k] = s2;
-  }
-}
-
-// one thread per (frame, subcarrier, rx-tx pair): the code groups in fixed order, G, and this
-// block's share of the residual variance (nv_part[f][rt][block], summed in order by weights)
-__global__ __launch_bounds__(256) void ls_combine_kernel(LsArgs a) {
-  __shared__ double red[4];
-  const uint32_t rt = blockIdx.y, f = blockIdx.z;
-  const FrameInfo &I = a.info[f];
-  if (I.status != 0) return;
-  const uint32_t M = a.M, N = a.N, P = a.n_groups;
-  const uint32_t k = blockIdx.x * 256 + threadIdx.x;
-  double nv = 0.0;
-  if (k < M) {
-    const bool occ = a.occ_index[k] >= 0;
-    const double *pp = a.part + ((uint64_t)f * N * N + rt) * P * 3 * M;
-    double sr = 0.0, si = 0.0, s2 = 0.0;
-    for (uint32_t g = 0; g < P; g++) {
-      sr += pp[(uint64_t)g * 3 * M + k];
-      si += pp[(uint64_t)g * 3 * M + M + k];
-      s2 += pp[(uint64_t)g * 3 * M + 2 * M + k];
-    }
-    const uint32_t r = rt / N, t = rt % N;
-    const double bias = (a.keep_bias && r == t) ? 1.0 : 0.0;
-    a.G[(((uint64_t)f * M + k) * N + r) * N + t] =
-        occ ? make_float2((float)((bias + sr) * a.scale), (float)(si * a.scale))
-            : make_float2(0.0f, 0.0f);
-    if (occ) nv = s2 - (sr * sr + si * si) / (double)a.nac;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) nv += __shfl_xor(nv, off);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = nv;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    a.nv_part[(uint64_t)f * a.n_nvp + (uint64_t)rt * gridDim.x + blockIdx.x] =
-        red[0] + red[1] + red[2] + red[3];
-}
-
-// ------------------------------------------------------------------------------------
-// complex double Gauss-Jordan with partial pivoting (same algorithm as the oracle)
-struct cd { double re, im; };
-
-template <int N>
-MIMO_DEV bool cd_solve(cd (&A)[N][N], cd (&B)[N][N]) {
-#pragma unroll
-  for (int c = 0; c < N; c++) {
-    int piv = c;
-    double best = A[c][c].re * A[c][c].re + A[c][c].im * A[c][c].im;
-#pragma unroll
-    for (int rr = c + 1; rr < N; rr++) {
-      const double m = A[rr][c].re * A[rr][c].re + A[rr][c].im * A[rr][c].im;
-      if (m > best) { best = m; piv = rr; }
-    }
-    // swap rows c and piv with static indexing
-#pragma unroll
-    for (int rr = c + 1; rr < N; rr++) {
-      if (rr == piv) {
-#pragma unroll
-        for (int k = 0; k < N; k++) {
-          cd t1 = A[c][k]; A[c][k] = A[rr][k]; A[rr][k] = t1;
-          cd t2 = B[c][k]; B[c][k] = B[rr][k]; B[rr][k] = t2;
-        }
-      }
-    }
-    const cd d = A[c][c];
-    const double dd = d.re * d.re + d.im * d.im;
-    if (dd == 0.0) return false;
-    const cd inv = {d.re / dd, -d.im / dd};
-#pragma unroll
-    for (int k = 0; k < N; k++) {
-      const cd x = A[c][k], y = B[c][k];
-      A[c][k] = {x.re * inv.re - x.im * inv.im, x.re * inv.im + x.im * inv.re};
-      B[c][k] = {y.re * inv.re - y.im * inv.im, y.re * inv.im + y.im * inv.re};
-    }
-#pragma unroll
-    for (int rr = 0; rr < N; rr++) {
-      if (rr == c) continue;
-      const cd fct = A[rr][c];
-      if (fct.re == 0.0 && fct.im == 0.0) continue;
-#pragma unroll
-      for (int k = 0; k < N; k++) {
-        const cd x = A[c][k], y = B[c][k];
-        A[rr][k].re -= fct.re * x.re - fct.im * x.im;
-        A[rr][k].im -= fct.re * x.im + fct.im * x.re;
-        B[rr][k].re -= fct.re * y.re - fct.im * y.im;
-        B[rr][k].im -= fct.re * y.im + fct.im * y.re;
-      }
-    }
-  }
-  return true;
-}
-
-template <int N>
-__global__ __launch_bounds__(256) void weights_kernel(WeightArgs a) {
-  const uint32_t f = blockIdx.y;
-  FrameInfo &I = a.info[f];
-  if (I.status != 0) return;
-  const uint32_t k = blockIdx.x * 256 + threadIdx.x;
-  // noise variance (same double expression as the oracle) and replay bookkeeping
-  double s2 = (double)a.noise_var;
-  if (a.noise_var < 0.0f) {
-    // the residual-variance partials, summed by wave 0 in a fixed order (lane-strided, then a
-    // fixed shuffle tree) and broadcast through LDS
-    __shared__ double s_acc;
-    if (threadIdx.x < 64) {
-      double acc = 0.0;
-      for (uint32_t e = threadIdx.x; e < a.n_nvp; e += 64)
-        acc += a.nv_part[(uint64_t)f * a.n_nvp + e];
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-      if (threadIdx.x == 0) s_acc = acc;
-    }
-    __syncthreads();
-    s2 = (double)(float)(s_acc * a.nv_norm);
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    I.noise_var = (float)s2;
-    // replay from corr_indices[N-1][N*nac-1] + M (framing.cc:857, generalised from [1])
-    const unsigned long long key =
-        a.keys[((uint64_t)f * N + (N - 1)) * a.n_slots + a.n_slots - 1];
-    const uint32_t ci = key ? (0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull)) : 0u;
-    const uint64_t i0 = (uint64_t)ci + a.M;
-    I.i0 = (uint32_t)i0;
-    I.n_sym = (i0 < a.win_len) ? (uint32_t)((a.win_len - i0) / a.SL) : 0u;
-  }
-  if (k >= a.M) return;
-  const float2 *g = a.G + ((uint64_t)f * a.M + k) * N * N;
-  float2 W[N][N];
-  float gain = 1.0f;
-  if (a.occ_index[k] < 0) {
-#pragma unroll
-    for (int i = 0; i < N; i++)
-#pragma unroll
-      for (int j = 0; j < N; j++) W[i][j] = make_float2(0.0f, 0.0f);
-  } else if (a.detector == 0 || a.detector == 3) {  // reference 2x2 invert (framing.cc:1344)
-    if constexpr (N == 2) {
-      const float2 det = csub(cmul(g[0], g[3]), cmul(g[1], g[2]));
-      const float2 di = cconj(det);
-      W[0][0] = cmul(di, g[3]);
-      W[1][1] = cmul(di, g[0]);
-      W[1][0] = cmul(cneg(di), g[2]);
-      W[0][1] = cmul(cneg(di), g[1]);
-      gain = 1.0f / (det.x * det.x + det.y * det.y);
-    } else {
-#pragma unroll
-      for (int i = 0; i < N; i++)
-#pragma unroll
-        for (int j = 0; j < N; j++) W[i][j] = make_float2(i == j ? 1.0f : 0.0f, 0.0f);
-    }
-  } else {
-    cd A[N][N], B[N][N];
-    if (a.detector == 1) {  // ZF: W = G^-1
-#pragma unroll
-      for (int i = 0; i < N; i++)
-#pragma unroll
-        for (int j = 0; j < N; j++) {
-          A[i][j] = {(double)g[i * N + j].x, (double)g[i * N + j].y};
-          B[i][j] = {i == j ? 1.0 : 0.0, 0.0};
-        }
-    } else {                // MMSE: W = (G^H G + s2 I)^-1 G^H
-#pragma unroll
-      for (int i = 0; i < N; i++)
-#pragma unroll
-        for (int j = 0; j < N; j++) {
-          double sr = 0.0, si = 0.0;
-#pragma unroll
-          for (int rr = 0; rr < N; rr++) {
-            const double gar = g[rr * N + i].x, gai = g[rr * N + i].y;
-            const double gbr = g[rr * N + j].x, gbi = g[rr * N + j].y;
-            sr += gar * gbr + gai * gbi;
-            si += gar * gbi - gai * gbr;
-          }
-          A[i][j] = {sr + ((i == j) ? s2 : 0.0), si};
-          B[i][j] = {(double)g[j * N + i].x, -(double)g[j * N + i].y};
-        }
-    }
-    const bool ok = cd_solve<N>(A, B);
-#pragma unroll
-    for (int i = 0; i < N; i++)
-#pragma unroll
-      for (int j = 0; j < N; j++)
-        W[i][j] = ok ? make_float2((float)B[i][j].re, (float)B[i][j].im) : make_float2(0.f, 0.f);
-  }
-#pragma unroll
-  for (int t = 0; t < N; t++)
-#pragma unroll
-    for (int rr = 0; rr < N; rr++)
-      a.W[(((uint64_t)f * N + t) * N + rr) * a.M + k] = W[t][rr];
-  a.gain[(uint64_t)f * a.M + k] = gain;
-}
-
-// ------------------------------------------------------------------------------------
-// N = 8: the per-thread form above needs 2 N^2 complex doubles in registers (512 VGPRs at
-// 8x8) and spills to scratch. Here one subcarrier is solved by a group of 8 lanes, lane j
-// holding row j of [A | B] (4 N doubles). The same Gauss-Jordan with partial pivoting as
-// cd_solve / the oracle: a lane's `pos` is its row's current index in the oracle's row
-// array, so the pivot search (largest |a|^2 among rows >= c, the smallest index winning
-// ties = the oracle's strict '>' scan from c) and the row swap (two lanes exchange pos) follow
-// the oracle exactly. The normalised pivot row is broadcast through LDS.
-constexpr int kWRowT = 256;
-constexpr int kWRowG = kWRowT / 8;   // subcarriers per workgroup
-
-template <int N>
-__global__ __launch_bounds__(kWRowT) void weights_row_kernel(WeightArgs a) {
-  static_assert(N >= 2 && N <= 8, "row solve handles 2..8 streams");
-  const uint32_t f = blockIdx.y;
-  FrameInfo &I = a.info[f];
-  if (I.status != 0) return;
-  __shared__ float2 s_g[kWRowG][N * N];
-  __shared__ cd s_piv[kWRowG][2 * N];
-  __shared__ int s_sing[kWRowG];
-  __shared__ double s_acc;
-  const int tid = threadIdx.x, grp = tid >> 3, j = tid & 7;
-  const uint32_t k = blockIdx.x * kWRowG + grp;
-  double s2 = (double)a.noise_var;
-  if (a.noise_var < 0.0f) {   // fixed-order partial sum, as weights_kernel
-    if (tid < 64) {
-      double acc = 0.0;
-      for (uint32_t e = tid; e < a.n_nvp; e += 64) acc += a.nv_part[(uint64_t)f * a.n_nvp + e];
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-      if (tid == 0) s_acc = acc;
-    }
-    __syncthreads();
-    s2 = (double)(float)(s_acc * a.nv_norm);
-  }
-  if (blockIdx.x == 0 && tid == 0) {
-    I.noise_var = (float)s2;
-    const unsigned long long key =
-        a.keys[((uint64_t)f * N + (N - 1)) * a.n_slots + a.n_slots - 1];
-    const uint32_t ci = key ? (0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull)) : 0u;
-    const uint64_t i0 = (uint64_t)ci + a.M;
-    I.i0 = (uint32_t)i0;
-    I.n_sym = (i0 < a.win_len) ? (uint32_t)((a.win_len - i0) / a.SL) : 0u;
-  }
-  const bool live = k < a.M;
-  const bool occ = live && a.occ_index[k] >= 0;
-  if (live)
-    for (int e = j; e < N * N; e += 8) s_g[grp][e] = a.G[((uint64_t)f * a.M + k) * N * N + e];
-  __syncthreads();
-  const bool row = j < N;
-  cd A[N], B[N];
-  const float2 *g = s_g[grp];
-#pragma unroll
-  for (int c = 0; c < N; c++) {
-    A[c] = {0.0, 0.0};
-    B[c] = {0.0, 0.0};
-  }
-  if (row) {
-    if (a.detector == 1) {   // ZF: A = G, B = I
-#pragma unroll
-      for (int c = 0; c < N; c++) {
-        A[c] = {(double)g[j * N + c].x, (double)g[j * N + c].y};
-        B[c] = {c == j ? 1.0 : 0.0, 0.0};
-      }
-    } else {                 // MMSE: A = G^H G + s2 I, B = G^H
-#pragma unroll
-      for (int c = 0; c < N; c++) {
-        double sr = 0.0, si = 0.0;
-#pragma unroll
-        for (int rr = 0; rr < N; rr++) {
-          const double gar = g[rr * N + j].x, gai = g[rr * N + j].y;
-          const double gbr = g[rr * N + c].x, gbi = g[rr * N + c].y;
-          sr += gar * gbr + gai * gbi;
-          si += gar * gbi - gai * gbr;
-        }
-        A[c] = {sr + ((c == j) ? s2 : 0.0), si};
-        B[c] = {(double)g[c * N + j].x, -(double)g[c * N + j].y};
-      }
-    }
-  }
-  int pos = row ? j : 64;
-  bool ok = true;
-#pragma unroll
-  for (int c = 0; c < N; c++) {
-    // pivot: max |A[.][c]|^2 over rows with pos >= c, smallest pos on ties
-    double m = (row && pos >= c) ? A[c].re * A[c].re + A[c].im * A[c].im : -1.0;
-    int mp = (row && pos >= c) ? pos : 64;
-#pragma unroll
-    for (int off = 1; off < 8; off <<= 1) {
-      const double om = __shfl_xor(m, off);
-      const int op = __shfl_xor(mp, off);
-      if (om > m || (om == m && op < mp)) { m = om; mp = op; }
-    }
-    // swap: the row at pos c takes the pivot's place
-    if (pos == c) pos = mp;
-    else if (pos == mp) pos = c;
-    if (pos == c && row) {              // the pivot lane normalises and publishes its row
-      const cd d = A[c];
-      const double dd = d.re * d.re + d.im * d.im;
-      s_sing[grp] = dd == 0.0 ? 1 : 0;
-      if (dd != 0.0) {
-        const cd inv = {d.re / dd, -d.im / dd};
-#pragma unroll
-        for (int q = 0; q < N; q++) {
-          const cd x = A[q], y = B[q];
-          A[q] = {x.re * inv.re - x.im * inv.im, x.re * inv.im + x.im * inv.re};
-          B[q] = {y.re * inv.re - y.im * inv.im, y.re * inv.im + y.im * inv.re};
-          s_piv[grp][q] = A[q];
-          s_piv[grp][N + q] = B[q];
-        }
-      }
-    }
-    __syncthreads();
-    const bool sing = s_sing[grp] != 0;
-    ok = ok && !sing;
-    if (!sing && row && pos != c) {
-      const cd fct = A[c];
-      if (!(fct.re == 0.0 && fct.im == 0.0)) {
-#pragma unroll
-        for (int q = 0; q < N; q++) {
-          const cd x = s_piv[grp][q], y = s_piv[grp][N + q];
-          A[q].re -= fct.re * x.re - fct.im * x.im;
-          A[q].im -= fct.re * x.im + fct.im * x.re;
-          B[q].re -= fct.re * y.re - fct.im * y.im;
-          B[q].im -= fct.re * y.im + fct.im * y.re;
-        }
-      }
-    }
-    __syncthreads();
-  }
-  if (!live || !row) return;
-  // row `pos` of B is row `pos` of W (output stream pos); zero on a null carrier or a singular
-  // system (as weights_kernel); detectors other than ZF/MMSE keep the identity (weights_kernel)
-  const bool solve = a.detector == 1 || a.detector == 2;
-#pragma unroll
-  for (int rr = 0; rr < N; rr++) {
-    float2 w = make_float2(0.0f, 0.0f);
-    if (occ && solve && ok) w = make_float2((float)B[rr].re, (float)B[rr].im);
-    else if (occ && !solve && rr == pos) w = make_float2(1.0f, 0.0f);
-    a.W[(((uint64_t)f * N + pos) * N + rr) * a.M + k] = w;
-  }
-  if (j == 0) a.gain[(uint64_t)f * a.M + k] = 1.0f;
-}
-
-// ------------------------------------------------------------------------------------
-template <int LOG2M, int LOG2F>
-static void codes_dispatch_f(const CodesArgs &a, int log2F, hipStream_t s) {
-  if constexpr (LOG2F <= 14) {
-    if (log2F == LOG2F) {
-      constexpr int F = 1 << LOG2F;
-      const size_t shm = sizeof(float2) * lds_padded_len(F);
-      (void)hipFuncSetAttribute((const void *)codes_kernel<LOG2M, LOG2F>,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-      hipLaunchKernelGGL((codes_kernel<LOG2M, LOG2F>), dim3(a.n_slots), dim3(kEstT), shm, s, a);
-      return;
-    }
-    codes_dispatch_f<LOG2M, LOG2F + 1>(a, log2F, s);
-  }
-}
-
-template <int LOG2M>
-static void codes_dispatch(const CodesArgs &a, int log2M, int log2F, hipStream_t s) {
-  if constexpr (LOG2M <= 12) {
-    if (log2M == LOG2M) { codes_dispatch_f<LOG2M, LOG2M>(a, log2F, s); return; }
-    codes_dispatch<LOG2M + 1>(a, log2M, log2F, s);
-  }
-}
-
-void launch_codes(const CodesArgs &a, int log2M, int log2F, hipStream_t s) {
-  codes_dispatch<6>(a, log2M, log2F, s);
-}
-
-template <int LOG2F>
-static void search_dispatch(const SearchArgs &a, int log2F, uint32_t nf, hipStream_t s) {
-  if constexpr (LOG2F <= 13) {
-    if (log2F == LOG2F) {
-      const size_t shm = sizeof(float2) * lds_padded_len(1 << LOG2F);
-      dim3 grid(a.n_slots * a.N * a.n_lagc, nf);
-      if constexpr (LOG2F >= 10) {
-        (void)hipFuncSetAttribute((const void *)search_reg_kernel<LOG2F>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        hipLaunchKernelGGL(search_reg_kernel<LOG2F>, grid, dim3((1 << LOG2F) / 16), shm, s, a);
-      } else {
-        (void)hipFuncSetAttribute((const void *)search_kernel<LOG2F>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        hipLaunchKernelGGL(search_kernel<LOG2F>, grid, dim3(kEstT), shm, s, a);
-      }
-      return;
-    }
-    search_dispatch<LOG2F + 1>(a, log2F, nf, s);
-  }
-}
-
-void launch_search(const SearchArgs &a, int log2F, uint32_t n_frames, hipStream_t s) {
-  search_dispatch<7>(a, log2F, n_frames, s);
-}
-
-// search_ls_kernel instances: F = 2^10 .. 2^14 with F/M = 2, 4 or 8 (F is the smallest power
-// of two >= max(2 SL + M - 1, 2M), so F/M <= 8 for cp <= M)
-template <int LOG2F, int D>
-static bool search_ls_try(const SearchArgs &a, int log2F, int log2M, uint32_t nf, hipStream_t s) {
-  if constexpr (LOG2F <= 14) {
-    if constexpr (D <= 3) {
-      constexpr int LOG2M = LOG2F - D;
-      if (log2F == LOG2F && log2M == LOG2M) {
-        if (nf) {
-          // the segment image, then the LS transform's M/2 twiddles
-          const size_t shm = sizeof(float2) * (lds_padded_len(1 << LOG2F) + (1 << LOG2M) / 2);
-          // wave-local sub-transforms (F = 1024 B) unless RMIMO_SEARCH_WAVE=0 (A/B)
-          void (*kern)(SearchArgs) = nullptr;
-          if constexpr (LOG2F >= 10) {
-            if (search_ls_wave_enabled() && a.codespec_w)
-              kern = a.cfo_part ? (a.sc16 ? search_ls_wave_kernel<LOG2F, LOG2M, true, true>
-                                          : search_ls_wave_kernel<LOG2F, LOG2M, false, true>)
-                                : (a.sc16 ? search_ls_wave_kernel<LOG2F, LOG2M, true>
-                                          : search_ls_wave_kernel<LOG2F, LOG2M, false>);
-          }
-          if (!kern)
-            kern = a.cfo_part ? (a.sc16 ? search_ls_kernel<LOG2F, LOG2M, true, true>
-                                        : search_ls_kernel<LOG2F, LOG2M, false, true>)
-                              : (a.sc16 ? search_ls_kernel<LOG2F, LOG2M, true>
-                                        : search_ls_kernel<LOG2F, LOG2M, false>);
-          (void)hipFuncSetAttribute((const void *)kern,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-          dim3 grid(((a.n_slots + 1) / 2) * a.N, nf);
-          hipLaunchKernelGGL(kern, grid, dim3((1 << LOG2F) / 16), shm, s, a);
-        }
-        return true;
-      }
-      return search_ls_try<LOG2F, D + 1>(a, log2F, log2M, nf, s);
-    } else {
-      return search_ls_try<LOG2F + 1, 1>(a, log2F, log2M, nf, s);
-    }
-  }
-  return false;
-}
-
-// the search form, a parity-test switch: the wave-local search_ls_wave_kernel (F >= 1024), or
-// RMIMO_SEARCH_FORM=block: search_ls_kernel, the same two slots per transform with
-// workgroup-wide exchanges
-bool search_ls_wave_enabled() {
-  static const bool block = [] { const char *e = getenv("RMIMO_SEARCH_FORM"); return e && strcmp(e, "block") == 0; }();
-  return !block;
-}
-
-bool search_ls_supported(int log2F, int log2M) {
-  return search_ls_try<10, 1>(SearchArgs{}, log2F, log2M, 0, nullptr);
-}
-
-bool launch_search_ls(const SearchArgs &a, int log2F, int log2M, uint32_t n_frames, hipStream_t s) {
-  return search_ls_try<10, 1>(a, log2F, log2M, n_frames, s);
-}
-
 // ------------------------------------------------------------------------------------
 // LS estimate of one (frame, rx, tx) straight from its nac access-code windows (framing.cc:
 // 797-824): workgroup (rx tx, frame), M/8 threads with 8 subcarriers each (k = lt + T e); per
@@ -1637,6 +978,87 @@ void ls_window_kernel(LsArgs a) {
   (void)NW;
 }
 
+template <int LOG2F>
+static void search_dispatch(const SearchArgs &a, int log2F, uint32_t nf, hipStream_t s) {
+  if constexpr (LOG2F <= 13) {
+    if (log2F == LOG2F) {
+      const size_t shm = sizeof(float2) * lds_padded_len(1 << LOG2F);
+      dim3 grid(a.n_slots * a.N * a.n_lagc, nf);
+      if constexpr (LOG2F >= 10) {
+        (void)hipFuncSetAttribute((const void *)search_reg_kernel<LOG2F>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+        hipLaunchKernelGGL(search_reg_kernel<LOG2F>, grid, dim3((1 << LOG2F) / 16), shm, s, a);
+      } else {
+        (void)hipFuncSetAttribute((const void *)search_kernel<LOG2F>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+        hipLaunchKernelGGL(search_kernel<LOG2F>, grid, dim3(kEstT), shm, s, a);
+      }
+      return;
+    }
+    search_dispatch<LOG2F + 1>(a, log2F, nf, s);
+  }
+}
+
+void launch_search(const SearchArgs &a, int log2F, uint32_t n_frames, hipStream_t s) {
+  search_dispatch<7>(a, log2F, n_frames, s);
+}
+
+// search_ls_kernel instances: F = 2^10 .. 2^14 with F/M = 2, 4 or 8 (F is the smallest power
+// of two >= max(2 SL + M - 1, 2M), so F/M <= 8 for cp <= M)
+template <int LOG2F, int D>
+static bool search_ls_try(const SearchArgs &a, int log2F, int log2M, uint32_t nf, hipStream_t s) {
+  if constexpr (LOG2F <= 14) {
+    if constexpr (D <= 3) {
+      constexpr int LOG2M = LOG2F - D;
+      if (log2F == LOG2F && log2M == LOG2M) {
+        if (nf) {
+          // the segment image, then the LS transform's M/2 twiddles
+          const size_t shm = sizeof(float2) * (lds_padded_len(1 << LOG2F) + (1 << LOG2M) / 2);
+          // wave-local sub-transforms (F = 1024 B) unless RMIMO_SEARCH_WAVE=0 (A/B)
+          void (*kern)(SearchArgs) = nullptr;
+          if constexpr (LOG2F >= 10) {
+            if (search_ls_wave_enabled() && a.codespec_w)
+              kern = a.cfo_part ? (a.sc16 ? search_ls_wave_kernel<LOG2F, LOG2M, true, true>
+                                          : search_ls_wave_kernel<LOG2F, LOG2M, false, true>)
+                                : (a.sc16 ? search_ls_wave_kernel<LOG2F, LOG2M, true>
+                                          : search_ls_wave_kernel<LOG2F, LOG2M, false>);
+          }
+          if (!kern)
+            kern = a.cfo_part ? (a.sc16 ? search_ls_kernel<LOG2F, LOG2M, true, true>
+                                        : search_ls_kernel<LOG2F, LOG2M, false, true>)
+                              : (a.sc16 ? search_ls_kernel<LOG2F, LOG2M, true>
+                                        : search_ls_kernel<LOG2F, LOG2M, false>);
+          (void)hipFuncSetAttribute((const void *)kern,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+          dim3 grid(((a.n_slots + 1) / 2) * a.N, nf);
+          hipLaunchKernelGGL(kern, grid, dim3((1 << LOG2F) / 16), shm, s, a);
+        }
+        return true;
+      }
+      return search_ls_try<LOG2F, D + 1>(a, log2F, log2M, nf, s);
+    } else {
+      return search_ls_try<LOG2F + 1, 1>(a, log2F, log2M, nf, s);
+    }
+  }
+  return false;
+}
+
+// the search form, a parity-test switch: the wave-local search_ls_wave_kernel (F >= 1024), or
+// RMIMO_SEARCH_FORM=block: search_ls_kernel, the same two slots per transform with
+// workgroup-wide exchanges
+bool search_ls_wave_enabled() {
+  static const bool block = [] { const char *e = getenv("RMIMO_SEARCH_FORM"); return e && strcmp(e, "block") == 0; }();
+  return !block;
+}
+
+bool search_ls_supported(int log2F, int log2M) {
+  return search_ls_try<10, 1>(SearchArgs{}, log2F, log2M, 0, nullptr);
+}
+
+bool launch_search_ls(const SearchArgs &a, int log2F, int log2M, uint32_t n_frames, hipStream_t s) {
+  return search_ls_try<10, 1>(a, log2F, log2M, n_frames, s);
+}
+
 // ls_window_kernel's limits: instances for 512 <= M <= 4096 (whole waves of M/8 threads; the
 // sign table LsArgs::s1sign_w exists for exactly these M), and with the opt-in CFO every code's
 // start phasor tabled in LDS
@@ -1666,50 +1088,6 @@ bool launch_ls_window(const LsArgs &a, int log2M, uint32_t n_frames, hipStream_t
   (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
   hipLaunchKernelGGL(kern, dim3(a.N * a.N, n_frames), dim3(T), shm, s, a);
   return true;
-}
-
-void launch_ls_combine_q(const LsArgs &a, uint32_t n_frames, hipStream_t s) {
-  hipLaunchKernelGGL(ls_combine_q_kernel, dim3((a.M + 255) / 256, a.N * a.N, n_frames), dim3(256),
-                     0, s, a);
-}
-
-template <int LOG2M>
-static void ls_dispatch(const LsArgs &a, int log2M, uint32_t nf, hipStream_t s) {
-  if constexpr (LOG2M <= 12) {
-    if (log2M == LOG2M) {
-      constexpr int M = 1 << LOG2M;
-      constexpr int T = M < 256 ? M : 256;
-      constexpr int CB = kLsCodesPerGroup;
-      const size_t shm = sizeof(float2) * lds_padded_len(M) * CB;
-      (void)hipFuncSetAttribute((const void *)ls_kernel<LOG2M, T, CB>,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-      hipLaunchKernelGGL((ls_kernel<LOG2M, T, CB>), dim3(a.N * a.N * a.n_groups, nf), dim3(T),
-                         shm, s, a);
-      hipLaunchKernelGGL(ls_combine_kernel, dim3((a.M + 255) / 256, a.N * a.N, nf), dim3(256),
-                         0, s, a);
-      return;
-    }
-    ls_dispatch<LOG2M + 1>(a, log2M, nf, s);
-  }
-}
-
-void launch_ls(const LsArgs &a, int log2M, uint32_t n_frames, hipStream_t s) {
-  ls_dispatch<6>(a, log2M, n_frames, s);
-}
-
-void launch_weights(const WeightArgs &a, uint32_t n_frames, hipStream_t s) {
-  dim3 grid((a.M + 255) / 256, n_frames);
-  switch (a.N) {
-    case 1: hipLaunchKernelGGL(weights_kernel<1>, grid, dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL(weights_kernel<2>, grid, dim3(256), 0, s, a); break;
-    case 3: hipLaunchKernelGGL(weights_kernel<3>, grid, dim3(256), 0, s, a); break;
-    case 4: hipLaunchKernelGGL(weights_kernel<4>, grid, dim3(256), 0, s, a); break;
-    default: {   // 8 streams (mimo_rx_create admits 1, 2, 4, 8): the 8-lane row solve
-      dim3 rgrid((a.M + kWRowG - 1) / kWRowG, n_frames);
-      hipLaunchKernelGGL(weights_row_kernel<8>, rgrid, dim3(kWRowT), 0, s, a);
-      break;
-    }
-  }
 }
 
 }  // namespace mimo

@@ -8,7 +8,8 @@
 
 namespace mimo {
 
-// Schmidl-Cox metric + plateau rule, framing.cc:591-637 (see sync_kernels.hip)
+// Schmidl-Cox metric + plateau rule, framing.cc:591-637 (see sc_common.hpp; sync_kernels.hip,
+// sc_item_kernels.hip, plateau_kernels.hip)
 struct ScRecord {             // a chunk's trigger candidate and the run starts it saw
   unsigned long long n_cand;
   unsigned long long start[kMaxStreams];
@@ -139,14 +140,14 @@ struct PlateauArgs {
 // one frame per capture: trigger -> run starts, sync index, window
 void launch_plateau(const PlateauArgs &a, uint32_t n_frames, hipStream_t s);
 // back-to-back frames per capture: the re-arm walk over the chunk candidates, the re-arm
-// certificates of frames k >= 1 and the chain fix-up (see sync_kernels.hip)
+// certificates of frames k >= 1 and the chain fix-up (see plateau_kernels.hip)
 void launch_stream_walk(const PlateauArgs &a, uint32_t n_caps, hipStream_t s);
 // DEBUG_LOG: the oracle-exact fp32 metric y of positions [lo, hi) of every antenna row
 // (framing.cc:598-600), out[row][i]
 void launch_sc_trace(const float2 *iq, uint64_t stride, uint32_t rows, uint32_t M, int64_t lo,
                      int64_t hi, float *out, hipStream_t s);
 
-// access-code search, framing.cc:702-744 (est_kernels.hip)
+// access-code search, framing.cc:702-744 (est_kernels.hip; the code tables: codes_kernels.hip)
 struct SearchArgs {
   const float2 *iq;
   int sc16;
@@ -175,7 +176,8 @@ bool search_ls_supported(int log2F, int log2M);
 // the wave-local form of search_ls_kernel (F >= 1024) is on (default; RMIMO_SEARCH_WAVE=0 turns it off)
 bool search_ls_wave_enabled();
 
-// LS estimate, framing.cc:797-824 (+ training residual noise variance)
+// LS estimate, framing.cc:797-824 (+ training residual noise variance) (ls_kernels.hip;
+// ls_window_kernel with the search's transforms in est_kernels.hip)
 struct LsArgs {
   const float2 *iq;
   uint64_t stride, frame_len;
@@ -213,7 +215,7 @@ bool launch_ls_window(const LsArgs &a, int log2M, uint32_t n_frames, hipStream_t
 // table), and under the opt-in CFO nac <= 256
 bool ls_window_supported(int log2M, uint32_t nac, bool cfo);
 
-// per-subcarrier weights, framing.cc:826-831 -> 1344-1367 (+ NxN ZF/MMSE)
+// per-subcarrier weights, framing.cc:826-831 -> 1344-1367 (+ NxN ZF/MMSE) (weights_kernels.hip)
 struct WeightArgs {
   uint32_t N, M, M_occ, nac, SL, n_slots;
   int detector;

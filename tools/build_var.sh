@@ -14,7 +14,9 @@ make -j8 >/dev/null
 base=$(basename $SRC .hip)
 base=$(basename $base .cpp)
 FLAGS=""
-case $base in sync_kernels|synth_kernels) FLAGS="-ffp-contract=off" ;; esac
+case $base in   # the Makefile's EXACT_OBJS
+  sync_kernels|sc_item_kernels|plateau_kernels|synth_kernels|soft_kernels|sic_kernels) FLAGS="-ffp-contract=off" ;;
+esac
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-result -I../../include \
   $FLAGS $DEFS -c $SRC -o $OUT/${base}_$NAME.o
 objs=$(ls $OBJ/*.o | grep -v "/$base.o\$")
