@@ -377,6 +377,71 @@ int mimo_rx_sic_soft(mimo_rx *h, const mimo_sic_soft *a, void *hip_stream);
  * linear filter at hand: T and C are not recomputed from the residual variances. */
 int mimo_rx_sic_soft_fb(mimo_rx *h, const mimo_sic_soft *a, void *hip_stream);
 
+/* ---------------- channel code over the int8 LLR rows: K = 7 Viterbi decoder (absent from the
+ * reference: it stops at modem_demodulate and has no channel code) ----
+ * An opt-in pass over a buffer of int8 LLRs such as a soft pass's d_llr (MIMO_LLR_I8); it needs
+ * no mimo_rx handle and the batch launches nothing for it. Integer arithmetic throughout: the
+ * output is defined to the bit (rub_mimo_amd/fec.py is this text as numpy).
+ *
+ * Encoder: the 802.11 mother code, K = 7, generators 133 / 171 octal. Info bits
+ * u_0..u_(n_info-1), then six zero tail bits: T = n_info + 6 trellis steps, u_t = 0 for t < 0;
+ * the trellis starts and ends in the all-zero state.
+ *   A_t = u_t ^ u_(t-2) ^ u_(t-3) ^ u_(t-5) ^ u_(t-6)     (133)
+ *   B_t = u_t ^ u_(t-1) ^ u_(t-2) ^ u_(t-3) ^ u_(t-6)     (171)
+ * Rates (the 802.11 puncturing patterns): MIMO_FEC_R12 sends every A_t and B_t; MIMO_FEC_R23 has
+ * period 2 and keeps A in steps {1,1}, B in {1,0}; MIMO_FEC_R34 has period 3 and keeps A in
+ * {1,1,0}, B in {1,0,1} (sent order A1 B1 A2 B3). Sent order: for t = 0..T-1, A_t if kept, then
+ * B_t if kept: coded bits k = 0..n_tx-1, so n_tx is 2T, floor(T/2) 3 + (T mod 2) 2 and
+ * floor(T/3) 4 + {0,2,3}[T mod 3].
+ *
+ * Rows: a codeword is one row of n_c values (one row of the soft passes' LLR buffers has
+ * n_c = M_occ 2b, contiguous in both output layouts). T is the largest step count with
+ * n_tx <= n_c; n_info = T - 6. Coded bit k is read at row position perm[k] (perm NULL: k); row
+ * positions no coded bit refers to are ignored. mimo_fec_create returns MIMO_ERR_ARG for a bad
+ * rate, T < 7, n_c > 32768 and a perm whose n_tx entries are not distinct values < n_c.
+ *
+ * Decoder: maximum likelihood over the terminated trellis with a full traceback from state 0,
+ * no truncation window. LLRs are positive for bit 0, as everywhere here; a punctured bit has
+ * LLR 0. The metric of a transition with outputs (a, b) is (a ? -L_A : L_A) + (b ? -L_B : L_B),
+ * L the plain int8 value (-128 is allowed and means -128) widened to int32. Path metrics are
+ * int32, 0 in state 0 and -2^30 in every other state at the start; the largest reachable
+ * magnitude is 2 128 24576 (6.3 M), so nothing is normalised and nothing wraps. At each state
+ * the larger metric survives; on equality the predecessor whose oldest bit u_(t-6) is 0.
+ *
+ * Outputs per row: the n_info decoded bits packed MSB first (bit k in byte k >> 3, mask
+ * 0x80 >> (k & 7)) at d_bits + row bits_pitch, every other bit and byte up to the pitch 0, and
+ * optionally the final path metric of state 0. A row of all-zero LLRs (what the soft passes
+ * write for unsynced frames and unwritten symbols) decodes to all-zero bits and metric 0. */
+enum { MIMO_FEC_R12 = 0, MIMO_FEC_R23 = 1, MIMO_FEC_R34 = 2 };
+typedef struct mimo_fec_config {
+  uint32_t rate;          /* MIMO_FEC_* */
+  uint32_t n_c;           /* values per row */
+  const uint16_t *perm;   /* host, n_tx entries, copied; or NULL (identity) */
+} mimo_fec_config;
+typedef struct mimo_fec mimo_fec;
+/* create, destroy, geometry and encode run on the host and touch no GPU */
+int mimo_fec_create(const mimo_fec_config *c, mimo_fec **out);
+int mimo_fec_destroy(mimo_fec *f);
+int mimo_fec_geometry(const mimo_fec *f, uint32_t *steps, uint32_t *n_info, uint32_t *n_tx);
+/* setup / test time: info[n_info] (0/1 bytes) -> row[n_c] (0/1 bytes at row positions, i.e.
+ * after perm; unreferenced positions 0) */
+int mimo_fec_encode(const mimo_fec *f, const uint8_t *info, uint8_t *row);
+typedef struct mimo_fec_decode_args {
+  const void *d_llr;      /* [n_rows][n_c] int8, 16-byte aligned */
+  void *d_bits;           /* [n_rows][bits_pitch] uint8, 16-byte aligned */
+  void *d_metric;         /* [n_rows] int32, or NULL */
+  uint32_t n_rows;
+  uint32_t bits_pitch;    /* bytes per output row: a multiple of 4, >= ceil(n_info / 8) */
+} mimo_fec_decode_args;
+/* Asynchronous on hip_stream (NULL: the default stream), no host synchronisation; the caller
+ * orders it after whatever wrote d_llr. The first decode of a handle creates the device copy of
+ * the position table and the survivor-decision workspace, both sized by the launch grid (the
+ * device's CU count) and never by n_rows; later calls allocate nothing and can be captured into
+ * a graph. MIMO_ERR_ARG for a null f, a, d_llr or d_bits, a misaligned pointer, n_rows = 0 and a
+ * bad bits_pitch; MIMO_ERR_HIP / MIMO_ERR_NOMEM as elsewhere. Single-caller-thread per handle,
+ * and one decode of a handle in flight at a time (the workspace is the handle's). */
+int mimo_fec_decode(mimo_fec *f, const mimo_fec_decode_args *a, void *hip_stream);
+
 /* stage timing with HIP events on the handle's launch stream (for the roofline line).
  * stages: 0 S&C, 1 plateau, 2 search, 3 LS, 4 weights, 5 decode, 6 EVM reduce; an sc16 batch
  * that is widened internally (not read in place) adds its widening launch to stage 0 */

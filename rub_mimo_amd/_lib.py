@@ -28,6 +28,8 @@ LAYOUT_STREAM_MAJOR, LAYOUT_SYMBOL_MAJOR = 0, 1
 STAGES_ALL, STAGES_FRONT, STAGES_DECODE = 0, 1, 2
 # mimo_soft_demap.format: int8 (rounded, clamped to +-127) or fp32 LLRs
 LLR_I8, LLR_F32 = 0, 1
+# mimo_fec_config.rate: the 802.11 K = 7 code at rate 1/2, 2/3, 3/4
+FEC_R12, FEC_R23, FEC_R34 = 0, 1, 2
 
 
 class RxConfig(C.Structure):
@@ -67,6 +69,15 @@ class SicSoft(C.Structure):
                 ("d_out_idx", C.c_void_p), ("n_frames", C.c_uint32),
                 ("max_out_syms", C.c_uint32), ("out_layout", C.c_uint32),
                 ("format", C.c_uint32), ("llr_scale", C.c_float)]
+
+
+class FecConfig(C.Structure):
+    _fields_ = [("rate", C.c_uint32), ("n_c", C.c_uint32), ("perm", C.c_void_p)]
+
+
+class FecDecodeArgs(C.Structure):
+    _fields_ = [("d_llr", C.c_void_p), ("d_bits", C.c_void_p), ("d_metric", C.c_void_p),
+                ("n_rows", C.c_uint32), ("bits_pitch", C.c_uint32)]
 
 
 class FrameResult(C.Structure):
@@ -121,6 +132,11 @@ SIGNATURES = {
     "mimo_rx_sic_soft_fb": (C.c_int, [_vp, _P(SicSoft), _vp]),
     "mimo_rx_sic_order": (C.c_int, [_vp, _vp, _u32]),
     "mimo_rx_sic_mse": (C.c_int, [_vp, _vp, _u32]),
+    "mimo_fec_create": (C.c_int, [_P(FecConfig), _P(_vp)]),
+    "mimo_fec_destroy": (C.c_int, [_vp]),
+    "mimo_fec_geometry": (C.c_int, [_vp, _P(_u32), _P(_u32), _P(_u32)]),
+    "mimo_fec_encode": (C.c_int, [_vp, _vp, _vp]),
+    "mimo_fec_decode": (C.c_int, [_vp, _P(FecDecodeArgs), _vp]),
     "mimo_rx_set_timing": (C.c_int, [_vp, C.c_int]),
     "mimo_rx_get_stage_times": (C.c_int, [_vp, _P(C.c_double), _P(_u32)]),
     "mimo_rx_get_sc_exact_count": (C.c_int, [_vp, _P(_u64)]),

@@ -415,6 +415,23 @@ struct SicPassArgs {
 // false when (N, bits) has no instance or the batch shape does not fit (nothing launched)
 bool launch_sic_pass(const SicPassArgs &a, uint32_t n_frames, hipStream_t s);
 
+// K = 7 Viterbi decoder over rows of int8 LLRs (fec_kernels.hip; mimo_fec_decode): one wave per
+// row, lane = state, persistent waves striding over the rows
+constexpr uint32_t kFecChunk = 64;          // trellis steps per decision chunk (one word per lane)
+constexpr uint32_t kFecBlock = 256;         // threads per workgroup: 4 waves, 4 rows in flight
+constexpr uint32_t kFecPunctured = 0xFFFFu; // position-table entry of a punctured bit
+struct FecArgs {
+  const int8_t *llr;               // [n_rows][n_c]
+  uint8_t *bits;                   // [n_rows][4 pitch_dw]
+  int32_t *metric;                 // [n_rows] or null
+  const uint32_t *pos;             // [chunks kFecChunk] row position of A_t | of B_t << 16
+                                   // (kFecPunctured: LLR 0; steps >= T padded with it)
+  unsigned long long *ws;          // [grid waves][chunks kFecChunk] survivor decisions
+  uint32_t n_rows, n_c, T, chunks, pitch_dw;
+};
+// blocks <= the grid the workspace was sized for
+void launch_fec_viterbi(const FecArgs &a, uint32_t blocks, hipStream_t s);
+
 // code tables: S0/S1 -> IFFT*dn (framing.cc:1054-1111, 1214-1262) -> zero-pad FFT_F
 struct CodesArgs {
   uint32_t M, N, nac, n_slots;
