@@ -31,8 +31,10 @@ MIMO_DEV int ring_pad(int i) { return i + ((i >> 5) << 1); }
 // matter -- are provisionally 1 and recomputed exactly as the CPU oracle does (sequential fp32
 // sums oldest->newest, no FMA: the S&C files are compiled with -ffp-contract=off) once the item
 // still has a candidate. A sequential fp32 sum of M terms is within (M-1)u of the exact
-// value, so |y32 - y_exact| <= ~4e-4 for M <= 2048; a 2e-3 band keeps every
-// plateau decision -- hence plateau start/end and sync_index -- bit-identical to the oracle.
+// value, so |y32 - y_exact| <= ~4.2e-4 for M <= 2048; the band sc_band(M), 1.25 x
+// that bound (about 5.2e-4 at M = 2048, 6.6e-5 at M = 256), keeps every plateau decision --
+// hence plateau start/end and sync_index -- bit-identical to the oracle. A sample that finds
+// the deferred list full is provisionally 1 as well and recomputed by its own lane (sc_exact).
 // An all-zero window (R = 0, the oracle's 0/0) is tracked exactly with a nonzero count.
 
 // exact restatement of framing.cc:626-637 under the pinned liquid semantics, on the M

@@ -411,11 +411,11 @@ __global__ __launch_bounds__(kScT) __attribute__((amdgpu_waves_per_eu(2))) void 
               const double q = Pre * Pre + Pim * Pim - a.thr * R2;
               if (fabs(q) <= a.band * R2 || Z <= zfloor) {
                 const int slot = atomicAdd(&s_namb, 1);
+                b = true;                 // provisional: the recompute clears it
                 if (slot < kAmbMax) {
                   amb_n[slot] = n;
                   amb_pos[slot] = n;
                   amb_s[slot] = (uint8_t)s;
-                  b = true;
                 } else {
                   ovf |= 1u << (i + h);   // list full: this lane recomputes it below
                 }

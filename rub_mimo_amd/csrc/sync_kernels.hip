@@ -513,9 +513,9 @@ void sc_exact_kernel(ScArgs a) {
           const double q = Pre * Pre + Pim * Pim - a.thr * R2;
           if (fabs(q) <= a.band * R2 || Z <= zfloor) {
             const int k = atomicAdd(&s_namb, 1);
+            b = true;                  // provisional: the recompute below clears it
             if (k < kLocAmb) {
-              s_amb[k] = n;
-              b = true;                // provisional: resolved below, from the ring
+              s_amb[k] = n;            // resolved from the ring
             } else {
               ovf |= 1u << (i + h);   // list full: this lane recomputes it below
             }
