@@ -442,6 +442,64 @@ typedef struct mimo_fec_decode_args {
  * and one decode of a handle in flight at a time (the workspace is the handle's). */
 int mimo_fec_decode(mimo_fec *f, const mimo_fec_decode_args *a, void *hip_stream);
 
+/* ---- soft-output (max-log-MAP) decoder for the same code: soft in, soft out ----
+ * Same code, rates, rows, perm, geometry and mimo_fec handle as mimo_fec_decode. LLRs are
+ * positive for bit 0, a punctured bit has LLR 0, and the int8 values are used plain (-128 is
+ * -128).
+ *
+ * Branch metric: same as Viterbi. g_t(p->s) = (a ? -L_A : L_A) + (b ? -L_B : L_B) for the
+ *   outputs (a, b) of the transition.
+ * Forward: alpha_0 = 0 in state 0 and NEG elsewhere. alpha_(t+1)(s) = max over the two
+ *   predecessors of alpha_t(p) + g_t(p->s).
+ * Backward: beta_T = 0 in state 0 and NEG elsewhere. beta_t(p) = max over the two successors of
+ *   g_t(p->s) + beta_(t+1)(s).
+ * NEG = -2^29, not Viterbi's -2^30. For T < 12 a state can be unreachable from both ends, so
+ *   alpha + g + beta goes down to about -2^30. With -2^30 as the start it would wrap int32. The
+ *   model's minimum over T = 7..13 is -2^30 - 140 and fits.
+ * No normalisation. Everything is int32 (the model computes in int64 and asserts the int32
+ *   range). Max and plus without overflow are exact in any order. So any evaluation order on the
+ *   GPU gives the same integers.
+ * Per-bit APP. For x in {u_t, A_t, B_t}: M_t^x(v) = max over transitions with x = v of
+ *   alpha_t(p) + g_t(p->s) + beta_(t+1)(s), and Lambda_t^x = M(0) - M(1). Where one hypothesis
+ *   has no path through the terminated trellis (this occurs for a few coded bits only at T = 7,
+ *   8), Lambda is about +-2^29 with the right sign. The integer arithmetic defines it.
+ *
+ * Outputs per row:
+ *   d_out[row][pos], int8, for every row position that a kept coded bit refers to. With
+ *     MIMO_FEC_SISO_APP the value is clamp(Lambda, -127, 127). With MIMO_FEC_SISO_EXT it is
+ *     clamp(Lambda - L_in, -127, 127), with the subtraction done in int32 before the clamp.
+ *     Positions no coded bit refers to are not written. d_out must not overlap d_llr;
+ *     overlapping ranges return MIMO_ERR_ARG.
+ *   d_bits (optional): info bit k = (Lambda_k^u < 0). Packing, pitch and zero padding are exactly
+ *     those of mimo_fec_decode. A tie (Lambda = 0) gives bit 0. This is not Viterbi's tie rule, so
+ *     the bits equal mimo_fec_decode's only in rows without a zero Lambda^u.
+ *   d_info_llr (optional): [n_rows][info_pitch] int8, clamp(Lambda_k^u, +-127) for k < n_info.
+ *     Bytes up to the pitch are 0. info_pitch is a multiple of 4 and >= n_info.
+ *   d_metric (optional): alpha_T(0). This is bitwise the metric mimo_fec_decode writes for the
+ *     same row.
+ * All-zero row. It gives all-zero d_out values at the used positions, zero bits, zero info LLRs
+ * and metric 0 (for T >= 12). At T < 12 the impossible-hypothesis positions saturate to +-127.
+ *
+ * At least one of d_out, d_bits and d_info_llr must be non-null. Error codes, alignment rules
+ * and threading are those of mimo_fec_decode: d_llr, d_out, d_bits and d_info_llr 16-byte and
+ * d_metric 4-byte aligned; MIMO_ERR_ARG for a null f, a or d_llr, all three outputs null, a
+ * misaligned pointer, n_rows = 0, a bad mode, a bad bits_pitch (with d_bits) or info_pitch (with
+ * d_info_llr) and overlapping d_out / d_llr. Asynchronous on hip_stream, single caller thread per
+ * handle, one call of a handle in flight. The first call allocates; later calls allocate nothing
+ * and can be captured into a graph. The workspace (alpha checkpoints every 64 steps, sized by the
+ * launch grid and never by n_rows) is the soft-output pass's own, created by a handle's first
+ * mimo_fec_siso call: a handle that never calls it pays nothing. */
+enum { MIMO_FEC_SISO_APP = 0, MIMO_FEC_SISO_EXT = 1 };
+typedef struct mimo_fec_siso_args {
+  const void *d_llr;    /* [n_rows][n_c] int8 */
+  void *d_out;          /* [n_rows][n_c] int8, or NULL */
+  void *d_bits;         /* [n_rows][bits_pitch] uint8, or NULL */
+  void *d_info_llr;     /* [n_rows][info_pitch] int8, or NULL */
+  void *d_metric;       /* [n_rows] int32, or NULL */
+  uint32_t n_rows, bits_pitch, info_pitch, mode;
+} mimo_fec_siso_args;
+int mimo_fec_siso(mimo_fec *f, const mimo_fec_siso_args *a, void *hip_stream);
+
 /* stage timing with HIP events on the handle's launch stream (for the roofline line).
  * stages: 0 S&C, 1 plateau, 2 search, 3 LS, 4 weights, 5 decode, 6 EVM reduce; an sc16 batch
  * that is widened internally (not read in place) adds its widening launch to stage 0 */

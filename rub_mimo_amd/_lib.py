@@ -30,6 +30,8 @@ STAGES_ALL, STAGES_FRONT, STAGES_DECODE = 0, 1, 2
 LLR_I8, LLR_F32 = 0, 1
 # mimo_fec_config.rate: the 802.11 K = 7 code at rate 1/2, 2/3, 3/4
 FEC_R12, FEC_R23, FEC_R34 = 0, 1, 2
+# mimo_fec_siso_args.mode: a-posteriori or extrinsic LLRs of the coded bits
+FEC_SISO_APP, FEC_SISO_EXT = 0, 1
 
 
 class RxConfig(C.Structure):
@@ -78,6 +80,12 @@ class FecConfig(C.Structure):
 class FecDecodeArgs(C.Structure):
     _fields_ = [("d_llr", C.c_void_p), ("d_bits", C.c_void_p), ("d_metric", C.c_void_p),
                 ("n_rows", C.c_uint32), ("bits_pitch", C.c_uint32)]
+
+
+class FecSisoArgs(C.Structure):
+    _fields_ = [("d_llr", C.c_void_p), ("d_out", C.c_void_p), ("d_bits", C.c_void_p),
+                ("d_info_llr", C.c_void_p), ("d_metric", C.c_void_p), ("n_rows", C.c_uint32),
+                ("bits_pitch", C.c_uint32), ("info_pitch", C.c_uint32), ("mode", C.c_uint32)]
 
 
 class FrameResult(C.Structure):
@@ -137,6 +145,7 @@ SIGNATURES = {
     "mimo_fec_geometry": (C.c_int, [_vp, _P(_u32), _P(_u32), _P(_u32)]),
     "mimo_fec_encode": (C.c_int, [_vp, _vp, _vp]),
     "mimo_fec_decode": (C.c_int, [_vp, _P(FecDecodeArgs), _vp]),
+    "mimo_fec_siso": (C.c_int, [_vp, _P(FecSisoArgs), _vp]),
     "mimo_rx_set_timing": (C.c_int, [_vp, C.c_int]),
     "mimo_rx_get_stage_times": (C.c_int, [_vp, _P(C.c_double), _P(_u32)]),
     "mimo_rx_get_sc_exact_count": (C.c_int, [_vp, _P(_u64)]),

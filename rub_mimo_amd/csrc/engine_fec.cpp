@@ -1,8 +1,9 @@
 // rub_mimo_amd/csrc/engine_fec.cpp -- the channel code over the int8 LLR rows: the mimo_fec
-// handle (geometry, position table, host encoder) and mimo_fec_decode, the launch of the
-// wave-per-row Viterbi decoder (fec_kernels.hip). Independent of mimo_rx: an opt-in pass over a
-// buffer of LLRs that the batch launches nothing for. create, geometry, encode and destroy touch
-// no GPU.
+// handle (geometry, position table, host encoder), mimo_fec_decode, the launch of the
+// wave-per-row Viterbi decoder (fec_kernels.hip), and mimo_fec_siso, the launch of the
+// max-log-MAP decoder on the same grid (fec_siso_kernels.hip). Independent of mimo_rx: opt-in
+// passes over a buffer of LLRs that the batch launches nothing for. create, geometry, encode and
+// destroy touch no GPU.
 #include <new>
 
 #include "engine_internal.hpp"
@@ -12,10 +13,16 @@ struct mimo_fec {
   // row position of A_t | of B_t << 16 per step (kFecPunctured: not sent), perm and puncturing
   // resolved; chunks * kFecChunk entries, the steps past T punctured
   std::vector<uint32_t> pos;
-  // ---- created by the first decode, sized by the grid ----
-  uint32_t max_blocks = 0;
+  // ---- created by the first decode or soft-output call, sized by the grid ----
+  uint32_t grid_blocks = 0;        // the persistent grid; set once d_pos is uploaded
   DevBuf<uint32_t> d_pos;
+  // ---- created by the first decode ----
+  uint32_t max_blocks = 0;
   DevBuf<unsigned long long> ws;   // [max_blocks * waves per block][chunks * kFecChunk]
+  // ---- created by the first soft-output call ----
+  uint32_t siso_blocks = 0;
+  // [siso_blocks * waves per block][(chunks + kFecChunk) * kFecChunk]
+  DevBuf<int32_t> ws_siso;
 };
 
 namespace {
@@ -38,7 +45,9 @@ uint32_t fec_n_tx(const Pattern &p, uint32_t T) {
   return T / p.period * per + n;
 }
 
-int fec_first_decode(mimo_fec *f, hipStream_t s) {
+// the persistent grid and the device copy of the position table, shared by both decoders
+int fec_grid(mimo_fec *f, hipStream_t s) {
+  if (f->grid_blocks) return MIMO_OK;
   int dev = 0, ncu = 0;
   HIPCHK(hipGetDevice(&dev));
   HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
@@ -50,14 +59,38 @@ int fec_first_decode(mimo_fec *f, hipStream_t s) {
   }
   const uint32_t wpb = kFecBlock / 64;
   const uint32_t blocks = (uint32_t)ncu * wpc / wpb;
-  const size_t words = (size_t)blocks * wpb * f->chunks * kFecChunk;
-  if (f->d_pos.ensure(f->pos.size()) != hipSuccess || f->ws.ensure(words) != hipSuccess) {
+  if (f->d_pos.ensure(f->pos.size()) != hipSuccess) {
     (void)hipGetLastError();
-    return fail(MIMO_ERR_NOMEM, "Viterbi position table and decision workspace");
+    return fail(MIMO_ERR_NOMEM, "channel code position table");
   }
   HIPCHK(hipMemcpyAsync(f->d_pos.p, f->pos.data(), sizeof(uint32_t) * f->pos.size(),
                         hipMemcpyHostToDevice, s));
-  f->max_blocks = blocks;
+  f->grid_blocks = blocks;
+  return MIMO_OK;
+}
+
+int fec_first_decode(mimo_fec *f, hipStream_t s) {
+  const int rc = fec_grid(f, s);
+  if (rc) return rc;
+  const size_t words = (size_t)f->grid_blocks * (kFecBlock / 64) * f->chunks * kFecChunk;
+  if (f->ws.ensure(words) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(MIMO_ERR_NOMEM, "Viterbi decision workspace");
+  }
+  f->max_blocks = f->grid_blocks;
+  return MIMO_OK;
+}
+
+int fec_first_siso(mimo_fec *f, hipStream_t s) {
+  const int rc = fec_grid(f, s);
+  if (rc) return rc;
+  const size_t words = (size_t)f->grid_blocks * (kFecBlock / 64) * (f->chunks + kFecChunk) *
+                       kFecChunk;
+  if (f->ws_siso.ensure(words) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(MIMO_ERR_NOMEM, "soft-output decoder checkpoint workspace");
+  }
+  f->siso_blocks = f->grid_blocks;
   return MIMO_OK;
 }
 
@@ -149,6 +182,49 @@ int mimo_fec_decode(mimo_fec *f, const mimo_fec_decode_args *a, void *hip_stream
   k.pitch_dw = a->bits_pitch / 4;
   const uint32_t wpb = kFecBlock / 64;
   launch_fec_viterbi(k, std::min(f->max_blocks, (a->n_rows + wpb - 1) / wpb), s);
+  HIPCHK(hipGetLastError());
+  return MIMO_OK;
+}
+
+int mimo_fec_siso(mimo_fec *f, const mimo_fec_siso_args *a, void *hip_stream) {
+  if (!f || !a || !a->d_llr) return fail(MIMO_ERR_ARG, "null argument");
+  if (!a->d_out && !a->d_bits && !a->d_info_llr)
+    return fail(MIMO_ERR_ARG, "d_out, d_bits and d_info_llr are all null");
+  if (((uintptr_t)a->d_llr & 15u) || ((uintptr_t)a->d_out & 15u) ||
+      ((uintptr_t)a->d_bits & 15u) || ((uintptr_t)a->d_info_llr & 15u))
+    return fail(MIMO_ERR_ARG, "d_llr, d_out, d_bits and d_info_llr must be 16-byte aligned");
+  if ((uintptr_t)a->d_metric & 3u) return fail(MIMO_ERR_ARG, "d_metric must be 4-byte aligned");
+  if (a->n_rows == 0) return fail(MIMO_ERR_ARG, "n_rows is 0");
+  if (a->mode > MIMO_FEC_SISO_EXT)
+    return fail(MIMO_ERR_ARG, "mode must be MIMO_FEC_SISO_APP or MIMO_FEC_SISO_EXT");
+  if (a->d_bits && ((a->bits_pitch & 3u) || a->bits_pitch < (f->n_info + 7) / 8))
+    return fail(MIMO_ERR_ARG, "bits_pitch must be a multiple of 4 and >= ceil(n_info / 8)");
+  if (a->d_info_llr && ((a->info_pitch & 3u) || a->info_pitch < f->n_info))
+    return fail(MIMO_ERR_ARG, "info_pitch must be a multiple of 4 and >= n_info");
+  if (a->d_out) {
+    const uintptr_t bytes = (uintptr_t)a->n_rows * f->n_c;
+    const uintptr_t l = (uintptr_t)a->d_llr, o = (uintptr_t)a->d_out;
+    if (l < o + bytes && o < l + bytes) return fail(MIMO_ERR_ARG, "d_out overlaps d_llr");
+  }
+  hipStream_t s = (hipStream_t)hip_stream;
+  if (f->siso_blocks == 0) {
+    const int rc = fec_first_siso(f, s);
+    if (rc) return rc;
+  }
+  FecSisoArgs k{};
+  k.llr = reinterpret_cast<const int8_t *>(a->d_llr);
+  k.out = reinterpret_cast<int8_t *>(a->d_out);
+  k.bits = reinterpret_cast<uint8_t *>(a->d_bits);
+  k.info_llr = reinterpret_cast<int8_t *>(a->d_info_llr);
+  k.metric = reinterpret_cast<int32_t *>(a->d_metric);
+  k.pos = f->d_pos.p;
+  k.ws = f->ws_siso.p;
+  k.n_rows = a->n_rows; k.n_c = f->n_c; k.T = f->T; k.chunks = f->chunks;
+  k.pitch_dw = a->d_bits ? a->bits_pitch / 4 : 0;
+  k.info_pitch = a->d_info_llr ? a->info_pitch : 0;
+  k.ext = a->mode == MIMO_FEC_SISO_EXT;
+  const uint32_t wpb = kFecBlock / 64;
+  launch_fec_siso(k, std::min(f->siso_blocks, (a->n_rows + wpb - 1) / wpb), s);
   HIPCHK(hipGetLastError());
   return MIMO_OK;
 }

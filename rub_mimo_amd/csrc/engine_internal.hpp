@@ -4,7 +4,8 @@
 //   engine_stages.cpp  workspace growth and the stage drivers (sync, estimate, decode)
 //   engine_batch.cpp   mimo_rx_process_batch, the HIP-graph cache, batch getters, soft output
 //   engine_sic.cpp     mimo_rx_sic_detect, mimo_rx_sic_soft(_fb) and the getters: the SIC passes
-//   engine_fec.cpp     mimo_fec_*: the channel code's handle, host encoder and Viterbi launch
+//   engine_fec.cpp     mimo_fec_*: the channel code's handle, host encoder, Viterbi and
+//                      soft-output decoder launches
 //   engine_stream.cpp  mimo_rx_execute: the streaming framesync state machine, DEBUG_LOG
 //   engine_tx.cpp      transmitter, synthesiser, subcarrier-type and m-sequence helpers
 //   engine_diag.cpp    the RMIMO_* environment switches and the diagnostic reports

@@ -432,6 +432,23 @@ struct FecArgs {
 // blocks <= the grid the workspace was sized for
 void launch_fec_viterbi(const FecArgs &a, uint32_t blocks, hipStream_t s);
 
+// max-log-MAP decoder over the same rows (fec_siso_kernels.hip; mimo_fec_siso): the Viterbi
+// kernel's wave-per-row persistent grid and position table
+struct FecSisoArgs {
+  const int8_t *llr;               // [n_rows][n_c]
+  int8_t *out;                     // [n_rows][n_c] or null: APP / extrinsic LLRs of the kept bits
+  uint8_t *bits;                   // [n_rows][4 pitch_dw] or null
+  int8_t *info_llr;                // [n_rows][info_pitch] or null
+  int32_t *metric;                 // [n_rows] or null
+  const uint32_t *pos;             // the Viterbi kernel's table
+  int32_t *ws;                     // [grid waves][(chunks + kFecChunk) kFecChunk] alpha at every
+                                   // chunk start, then at every step of a part-filled last chunk
+  uint32_t n_rows, n_c, T, chunks, pitch_dw, info_pitch;
+  uint32_t ext;                    // 1: d_out = Lambda - L_in (MIMO_FEC_SISO_EXT)
+};
+// blocks <= the grid the workspace was sized for
+void launch_fec_siso(const FecSisoArgs &a, uint32_t blocks, hipStream_t s);
+
 // code tables: S0/S1 -> IFFT*dn (framing.cc:1054-1111, 1214-1262) -> zero-pad FFT_F
 struct CodesArgs {
   uint32_t M, N, nac, n_slots;

@@ -24,6 +24,17 @@ at 0 in state 0 and at -2^30 elsewhere, are never normalised (the largest reacha
 2 * 128 * 24576), the larger one survives and a tie keeps p0. Outputs per row: the n_info bits
 packed MSB first (bit k at byte k >> 3, mask 0x80 >> (k & 7)), zero up to the pitch, and the
 final metric of state 0. An all-zero row decodes to zero bits and metric 0.
+
+Soft-output decoder (mimo_fec_siso, DESIGN.md "Soft-output decoder"): max-log-MAP over the same
+trellis, branch metric g_t(p->s) and rows. alpha_0 and beta_T are 0 in state 0 and NEG = -2^29
+elsewhere (not -2^30: for T < 12 a state can be unreachable from both ends, and alpha + g + beta
+must stay in int32); alpha_(t+1)(s) = max over the two predecessors of alpha_t(p) + g_t(p->s),
+beta_t(p) = max over the two successors of g_t(p->s) + beta_(t+1)(s); nothing is normalised. For
+x in {u_t, A_t, B_t}: M(v) = max over the transitions with x = v of alpha_t(p) + g_t(p->s) +
+beta_(t+1)(s) and Lambda = M(0) - M(1). d_out receives clamp(Lambda, +-127) (APP) or
+clamp(Lambda - L_in, +-127) (EXT) at the row position of every kept coded bit and nothing
+elsewhere; info bit k is Lambda_k^u < 0 (a tie gives 0), the info LLR clamp(Lambda_k^u, +-127),
+the metric alpha_T(0), which is the Viterbi metric.
 """
 from __future__ import annotations
 
@@ -39,6 +50,8 @@ TAIL = 6
 N_STATES = 64
 MAX_NC = 32768
 M_INIT = -(1 << 30)
+NEG_SISO = -(1 << 29)
+SISO_APP, SISO_EXT = 0, 1
 # kept (1) / punctured (0) per step of the period, for A and for B
 KEEP = {R12: ((1,), (1,)), R23: ((1, 1), (1, 0)), R34: ((1, 1, 0), (1, 0, 1))}
 D_FREE = {R12: 10, R23: 6, R34: 5}
@@ -187,6 +200,75 @@ def decode(rate, n_c, llr, perm=None, bits_pitch=None):
     return pack_bits(bits, bits_pitch), metric.astype(np.int32)
 
 
+def _i32(x):
+    assert x.min() >= -(1 << 31) and x.max() < (1 << 31)
+    return x
+
+
+def siso(LA, LB):
+    """(L_A, L_B) [rows][T] integers -> (Lu, LAo, LBo [rows][T] int64, metric [rows] int64): the
+    unclamped max-log-MAP Lambda of u_t, A_t and B_t of the module docstring and alpha_T(0), in
+    int64 with every intermediate asserted to lie in int32; vectorised over rows and states."""
+    LA = np.asarray(LA).astype(np.int64)
+    LB = np.asarray(LB).astype(np.int64)
+    rows, T = LA.shape
+    (p0, sa0, sb0), (p1, sa1, sb1) = _trellis()          # the two transitions into state s
+    s = np.arange(N_STATES)
+    low = np.int64(-(1 << 62))                           # "no such transition" in a masked max
+    # per bit x and value v: which of the 2 * 64 transitions (into s from p0, into s from p1)
+    sel = {"u": [np.concatenate([s & 1, s & 1]) == v for v in (0, 1)],
+           "a": [np.concatenate([sa0, sa1]) == 1 - 2 * v for v in (0, 1)],
+           "b": [np.concatenate([sb0, sb1]) == 1 - 2 * v for v in (0, 1)]}
+    al = np.empty((T + 1, rows, N_STATES), np.int64)
+    al[0] = NEG_SISO
+    al[0][:, 0] = 0
+    for t in range(T):
+        la, lb = LA[:, t, None], LB[:, t, None]
+        al[t + 1] = _i32(np.maximum(al[t][:, p0] + (sa0 * la + sb0 * lb),
+                                    al[t][:, p1] + (sa1 * la + sb1 * lb)))
+    be = np.full((rows, N_STATES), NEG_SISO, np.int64)
+    be[:, 0] = 0
+    out = {k: np.empty((rows, T), np.int64) for k in sel}
+    for t in range(T - 1, -1, -1):
+        la, lb = LA[:, t, None], LB[:, t, None]
+        c0 = (sa0 * la + sb0 * lb) + be                  # g + beta_(t+1)(s), from p0 and from p1
+        c1 = (sa1 * la + sb1 * lb) + be
+        e = _i32(np.concatenate([al[t][:, p0] + c0, al[t][:, p1] + c1], 1))
+        for k, (m0, m1) in sel.items():
+            out[k][:, t] = _i32(np.where(m0, e, low).max(1) - np.where(m1, e, low).max(1))
+        # state p < 32 is p0 of s = 2p and 2p + 1, state p >= 32 is their p1
+        be = _i32(np.concatenate([np.maximum(c0[:, 0::2], c0[:, 1::2]),
+                                  np.maximum(c1[:, 0::2], c1[:, 1::2])], 1))
+    return out["u"], out["a"], out["b"], al[T][:, 0].copy()
+
+
+def decode_siso(rate, n_c, llr, perm=None, mode=SISO_APP, bits_pitch=None, info_pitch=None,
+                fill=0):
+    """llr [rows][n_c] int8 -> (out [rows][n_c] int8, packed bits [rows][bits_pitch] uint8,
+    info LLRs [rows][info_pitch] int8, metric [rows] int32): what mimo_fec_siso writes. `fill` is
+    what d_out held before the call: positions no kept coded bit refers to keep it."""
+    assert mode in (SISO_APP, SISO_EXT)
+    T, n_info, _ = geometry(rate, n_c)
+    LA, LB = depuncture(rate, n_c, llr, perm)
+    Lu, LAo, LBo, metric = siso(LA, LB)
+    if mode == SISO_EXT:
+        LAo, LBo = _i32(LAo - LA), _i32(LBo - LB)
+    pA, pB = positions(rate, n_c, perm)
+    out = np.full(np.asarray(llr).shape, fill, np.int8)
+    out[:, pA[pA >= 0]] = np.clip(LAo[:, pA >= 0], -127, 127)
+    out[:, pB[pB >= 0]] = np.clip(LBo[:, pB >= 0], -127, 127)
+    info_pitch = min_info_pitch(n_info) if info_pitch is None else info_pitch
+    info = np.zeros((LA.shape[0], info_pitch), np.int8)
+    info[:, :n_info] = np.clip(Lu[:, :n_info], -127, 127)
+    bits = pack_bits((Lu[:, :n_info] < 0).astype(np.uint8), bits_pitch)
+    return out, bits, info, metric.astype(np.int32)
+
+
+def min_info_pitch(n_info):
+    """The smallest info_pitch: n_info rounded up to a multiple of 4."""
+    return (n_info + 3) // 4 * 4
+
+
 def qam_indices(row, n_bits):
     """Coded rows [..., n_c] of 0/1 -> QAM indices [..., n_c / n_bits]: value i of a symbol is
     bit i of its index counted from the most significant bit (the soft passes' LLR order)."""
@@ -245,6 +327,22 @@ class Fec:
         a = _lib.FecDecodeArgs(_ptr(llr), _ptr(bits), _ptr(metric), n_rows,
                                self.min_pitch() if bits_pitch is None else bits_pitch)
         _lib.check(_lib.lib().mimo_fec_decode(self._h, C.byref(a), stream), "mimo_fec_decode")
+
+    def min_info_pitch(self):
+        return min_info_pitch(self.n_info)
+
+    def siso(self, llr, n_rows, out=None, bits=None, info_llr=None, metric=None, mode=SISO_APP,
+             bits_pitch=None, info_pitch=None, stream=None):
+        """Max-log-MAP decode of n_rows rows of n_c int8 LLRs on the device (mimo_fec_siso): out
+        (optional) receives the APP or extrinsic int8 LLRs of the kept coded bits at their row
+        positions, bits (optional) [n_rows][bits_pitch] uint8, info_llr (optional)
+        [n_rows][info_pitch] int8, metric (optional) [n_rows] int32. At least one of out, bits and
+        info_llr. Tensors, DeviceBuffers or addresses. Asynchronous on `stream`."""
+        from .receiver import _ptr
+        a = _lib.FecSisoArgs(_ptr(llr), _ptr(out), _ptr(bits), _ptr(info_llr), _ptr(metric),
+                             n_rows, self.min_pitch() if bits_pitch is None else bits_pitch,
+                             self.min_info_pitch() if info_pitch is None else info_pitch, mode)
+        _lib.check(_lib.lib().mimo_fec_siso(self._h, C.byref(a), stream), "mimo_fec_siso")
 
     @staticmethod
     def qam_indices(row, n_bits):
