@@ -377,6 +377,68 @@ int mimo_rx_sic_soft(mimo_rx *h, const mimo_sic_soft *a, void *hip_stream);
  * linear filter at hand: T and C are not recomputed from the residual variances. */
 int mimo_rx_sic_soft_fb(mimo_rx *h, const mimo_sic_soft *a, void *hip_stream);
 
+/* ---------------- soft-input MMSE-PIC: decoder priors into the detector ----
+ * The detector of an iterative receiver: it takes a-priori LLRs of the coded bits (such as
+ * mimo_fec_siso's MIMO_FEC_SISO_EXT output, which sits at the row positions of a soft pass's
+ * d_llr), turns them into each stream's expected symbol and variance, cancels every other
+ * stream's expected symbol (parallel interference cancellation), filters what is left with the
+ * MMSE filter of the residual covariance, recomputed per carrier and symbol, and writes extrinsic
+ * per-bit LLRs in the usual row layout. Opt-in and after the batch; unless stated otherwise the
+ * conditions, side-effect rules, shape checks and erased rows of mimo_rx_sic_soft apply, and it
+ * works with cfo_correct, with frames_per_capture > 1 and after MIMO_STAGES_DECODE.
+ *
+ * Per synced frame and occupied carrier, G, s2, Q = G^H G, lambda and R = Q + lambda I are as in
+ * the SIC section, and m = R y is the matched-filter statistic recovered from the decode's y.
+ * Per written symbol, for stream t = 0..N-1:
+ *   1. natural prior LLRs lam_i = prior[t][i] / prior_scale, from the plain int8 value (-128
+ *      means -128); positive = bit 0; bit order as the soft passes write it: values 0..b-1
+ *      belong to Re, most significant bit first, values b..2b-1 to Im.
+ *   2. prior moments per dimension over the L levels l_m of qam_point:
+ *      P(m) ~ exp(sum_i (bit_i(gray m) ? -lam_i / 2 : +lam_i / 2)), mean = sum P l,
+ *      variance = max(sum P l^2 - mean^2, 0); sbar_t = mean(Re) + j mean(Im),
+ *      v_t = variance(Re) + variance(Im).
+ *   3. A = Q diag(v) + s2 I, r = m - Q sbar, mu_t = (A^-1 Q)[t][t] (real).
+ *   4. z^_t = (A^-1 r)_t / mu_t + sbar_t, nu_t = 1 / mu_t - v_t.
+ *   5. idx_t = the decode's slicer of z^_t; LLR_i = llr_scale delta_i(z^_t) / max(nu_t, 1e-30),
+ *      with delta, the formats, the rounding and NaN -> 0 exactly those of mimo_rx_sic_soft.
+ * Steps 3-4 are the unbiased MMSE estimate of s_t from X - sum_{u != t} g_u sbar_u, whose
+ * residual covariance is G diag(v, with v_t := 1) G^H + s2 I, brought into the N x N domain by
+ * the push-through identity. Stream t's own priors enter neither z^_t nor nu_t: the output is
+ * extrinsic and can go straight back into the decoder.
+ *
+ * The moments are evaluated in the factorised form of the reflected Gray map (b exponentials per
+ * dimension, equal to the sum over the levels), and the solve is an elimination of A in fp32
+ * without pivoting: A is a column scaling of the Hermitian positive definite Q + s2 diag(v)^-1.
+ *
+ * Limits: d_prior NULL or all zero gives sbar = 0, v = 1 and every stream's unbiased linear MMSE
+ * output with nu_t = 1 / beta_t - 1 (for stream pi_0 that is mimo_rx_sic_soft's stage 0, as a
+ * mathematical identity, not a bitwise one; NULL is bitwise the zero buffer). Certain priors
+ * give nu_t = s2 / Q[t][t], the matched-filter bound. At N = 1 the priors cancel out of the
+ * result and are not read.
+ *
+ * These get LLR 0, z^ 0 and idx 0, and their priors are never read: rows the decode did not
+ * write, every carrier whose Q is not finite, and every frame with noise_var <= 0 (A can be
+ * singular there).
+ *
+ * MIMO_ERR_ARG: mimo_rx_sic_soft's cases, a prior_scale that is not finite and positive, a
+ * d_prior that is not 16-byte aligned or overlaps d_llr. MIMO_ERR_UNSUPPORTED: MIMO_DET_SISO,
+ * MIMO_DET_ZF2 at N != 2, N = 3, and N = 8: a per-symbol 8 x 8 solve does not fit the register
+ * file next to the rest of the pass. Instances exist for N = 1, 2, 4, b = 1..4, both formats. */
+typedef struct mimo_pic_soft {
+  const void *d_sym;      /* the last batch's d_out_sym */
+  const void *d_prior;    /* int8 a-priori LLRs, shape and layout of d_llr (MIMO_LLR_I8), or NULL = all 0 */
+  void *d_llr;            /* extrinsic LLRs, [d_sym's rows][M_occ][2b] int8 or float; required */
+  void *d_out_sym;        /* z^, complex64, as mimo_sic_soft.d_out_sym, or NULL */
+  void *d_out_idx;        /* the decode's slicer of z^, or NULL */
+  uint32_t n_frames, max_out_syms, out_layout;
+  uint32_t format;        /* MIMO_LLR_I8 / MIMO_LLR_F32, of d_llr */
+  float llr_scale;        /* of d_llr; finite, > 0 */
+  float prior_scale;      /* natural prior LLR = value / prior_scale; finite, > 0 */
+} mimo_pic_soft;
+/* Asynchronous on hip_stream (NULL: the handle's), no host synchronisation; allocates only when
+ * the slot count grows, so it can be captured into a graph after one warm-up call. */
+int mimo_rx_pic_soft(mimo_rx *h, const mimo_pic_soft *a, void *hip_stream);
+
 /* ---------------- channel code over the int8 LLR rows: K = 7 Viterbi decoder (absent from the
  * reference: it stops at modem_demodulate and has no channel code) ----
  * An opt-in pass over a buffer of int8 LLRs such as a soft pass's d_llr (MIMO_LLR_I8); it needs

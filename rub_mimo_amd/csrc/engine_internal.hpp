@@ -4,6 +4,7 @@
 //   engine_stages.cpp  workspace growth and the stage drivers (sync, estimate, decode)
 //   engine_batch.cpp   mimo_rx_process_batch, the HIP-graph cache, batch getters, soft output
 //   engine_sic.cpp     mimo_rx_sic_detect, mimo_rx_sic_soft(_fb) and the getters: the SIC passes
+//   engine_pic.cpp     mimo_rx_pic_soft: the soft-input MMSE-PIC pass
 //   engine_fec.cpp     mimo_fec_*: the channel code's handle, host encoder, Viterbi and
 //                      soft-output decoder launches
 //   engine_stream.cpp  mimo_rx_execute: the streaming framesync state machine, DEBUG_LOG
@@ -203,6 +204,10 @@ struct mimo_rx {
   DevBuf<float2> sic_T, sic_C;
   DevBuf<uint8_t> sic_order, sic_ok;
   DevBuf<float> sic_nu;
+  // soft-input MMSE-PIC (engine_pic.cpp): the packed Q = G^H G [F][N^2][M_occ] and the carrier
+  // flags [F][M_occ] of the last batch
+  DevBuf<float> pic_Q;
+  DevBuf<uint8_t> pic_ok;
   // ---- streaming state (facade) and debug buffers (in no captured graph) ----
   // The device capture holds samples [origin, origin + total) of the stream since
   // construction/reset (positions inside it are capture-relative).
@@ -300,6 +305,13 @@ int run_decode(mimo_rx *h, const Capture &c, uint32_t F, const DecodeRequest &q,
 // detector, noise variance, threshold) into its kernel nodes: any setter of such a scalar
 // drops the graphs so the next batch is launched (and later re-captured) with the new value.
 void invalidate_graph(mimo_rx *h);
+
+// ---- engine_sic.cpp ----
+// MIMO_OK when the handle's detector delivers y = (Q + lambda I)^-1 G^H X
+int sic_supported(const mimo_rx *h);
+// what the passes over the last batch's symbols ask of the handle and of the arguments they share
+int sic_pass_check(const mimo_rx *h, const void *d_sym, const void *d_out_sym, uint32_t n_frames,
+                   uint32_t max_out_syms, uint32_t out_layout);
 
 // ---- engine_diag.cpp ----
 struct DiagEnv {          // the engine's RMIMO_* switches, read once per process

@@ -6,7 +6,7 @@
 #include "engine_internal.hpp"
 
 // MIMO_OK when the handle's detector delivers y = (Q + lambda I)^-1 G^H X
-static int sic_supported(const mimo_rx *h) {
+int mimo::sic_supported(const mimo_rx *h) {
   if (h->det == MIMO_DET_SISO)
     return fail(MIMO_ERR_UNSUPPORTED, "SIC detection with the SISO detector");
   if (h->det == MIMO_DET_ZF2 && h->N != 2)
@@ -33,10 +33,10 @@ static int launch_batch_sic_tables(mimo_rx *h, uint32_t F, hipStream_t s) {
   return MIMO_OK;
 }
 
-// what mimo_rx_sic_detect and mimo_rx_sic_soft ask of the handle and of the arguments they
-// share (the callers have checked their pointers for null and alignment): a batch has run, its
+// what mimo_rx_sic_detect, mimo_rx_sic_soft and mimo_rx_pic_soft ask of the handle and of the
+// arguments they share (the callers have checked their pointers for null and alignment): a batch has run, its
 // detector is supported, the shape is that batch's and z does not land on d_sym
-static int sic_pass_check(const mimo_rx *h, const void *d_sym, const void *d_out_sym,
+int mimo::sic_pass_check(const mimo_rx *h, const void *d_sym, const void *d_out_sym,
                           uint32_t n_frames, uint32_t max_out_syms, uint32_t out_layout) {
   if (out_layout != MIMO_LAYOUT_STREAM_MAJOR && out_layout != MIMO_LAYOUT_SYMBOL_MAJOR)
     return fail(MIMO_ERR_ARG, "out_layout must be MIMO_LAYOUT_STREAM_MAJOR or _SYMBOL_MAJOR");

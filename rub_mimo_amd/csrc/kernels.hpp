@@ -415,6 +415,42 @@ struct SicPassArgs {
 // false when (N, bits) has no instance or the batch shape does not fit (nothing launched)
 bool launch_sic_pass(const SicPassArgs &a, uint32_t n_frames, hipStream_t s);
 
+// soft-input MMSE-PIC detection (pic_kernels.hip; mimo_rx_pic_soft): Q = G^H G per (frame,
+// occupied carrier), then one pass over the batch's equalised symbols that takes a-priori LLRs
+constexpr uint32_t pic_q_rows(uint32_t N) { return N * N; }   // floats of the packed Hermitian Q
+struct PicTableArgs {
+  uint32_t N, M, M_occ;
+  const int32_t *occ_index;
+  const float2 *G;                 // [F][M][N][N]
+  const FrameInfo *info;
+  float *Q;                        // [F][N^2][M_occ]: Q[t][t] in rows 0..N-1, then per pair t < u
+                                   // (row-major) Re Q[t][u], Im Q[t][u]
+  uint8_t *ok;                     // [F][M_occ]: 1 where the frame synced with noise_var > 0
+                                   // and every entry of Q is finite (all else is erased)
+};
+// false when N has no instance (nothing launched)
+bool launch_pic_tables(const PicTableArgs &a, uint32_t n_frames, hipStream_t s);
+
+struct PicPassArgs {
+  const float2 *sym;               // the batch's d_out_sym
+  const int8_t *prior;             // a-priori LLRs [sym's rows][M_occ][2 bits] int8, or null = 0
+  float2 *out_sym;                 // z-hat, same layout, or null
+  uint8_t *out_idx;                // demapped index of z-hat, same layout, or null
+  void *llr;                       // [sym's rows][M_occ][2 bits] int8 or float
+  uint32_t N, M_occ, max_out;
+  int symbol_major;                // rows [F][max_out][N] instead of [F][N][max_out]
+  int mmse;                        // lambda = s2 (MIMO_DET_MMSE) or 0
+  Qam qam;
+  const FrameInfo *info;
+  const float *Q;                  // PicTableArgs::Q
+  const uint8_t *ok;               // PicTableArgs::ok
+  float llr_scale, prior_scale;
+  int f32;                         // MIMO_LLR_F32
+  uint32_t bits;                   // per dimension (1..4)
+};
+// false when (N, bits) has no instance or the batch shape does not fit (nothing launched)
+bool launch_pic_pass(const PicPassArgs &a, uint32_t n_frames, hipStream_t s);
+
 // K = 7 Viterbi decoder over rows of int8 LLRs (fec_kernels.hip; mimo_fec_decode): one wave per
 // row, lane = state, persistent waves striding over the rows
 constexpr uint32_t kFecChunk = 64;          // trellis steps per decision chunk (one word per lane)

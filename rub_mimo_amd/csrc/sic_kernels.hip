@@ -15,9 +15,7 @@
 
 #include <type_traits>
 
-#include "fft.hpp"
-#include "kernels.hpp"
-#include "llr.hpp"
+#include "sic_pass.hpp"
 
 namespace mimo {
 
@@ -266,73 +264,11 @@ bool launch_sic_tables(const SicTableArgs &a, uint32_t n_frames, hipStream_t s) 
 // instances, the LLR drain of 4, the prologue of 1 (N = 8 64-QAM fp32, 12 -> 20 B of scratch);
 // the index drain alone kept all three figures but changed every instance's instruction
 // stream. Inline, on plain arrays, all 45 instances compile to the instruction streams of the
-// two kernels this one replaced, so their measured times stand.
-constexpr int kSicT = 128;
-constexpr int kSicSB = 32;      // symbols per workgroup
-template <int N>
-constexpr int sic_sc() { return N <= 2 ? 8 : (N <= 4 ? 4 : 2); }   // symbols per iteration
-
+// two kernels this one replaced, so their measured times stand. (kSicT, kSicSB, sic_sc, the
+// multiply-add, the slicer and the LLR image are in sic_pass.hpp: pic_kernels.hip shares them.)
 MIMO_DEV uint64_t sic_row(const SicPassArgs &a, uint32_t f, uint32_t t, uint32_t s) {
   return a.symbol_major ? ((uint64_t)f * a.max_out + s) * a.N + t
                         : ((uint64_t)f * a.N + t) * a.max_out + s;
-}
-
-// acc += a b as two packed fused multiply-adds: (a.x, a.x) b + (a.y, a.y) (-b.y, b.x); br is
-// (-b.y, b.x)
-MIMO_DEV v2f sic_mac(v2f acc, float2 a, v2f b, v2f br) {
-  v2f ax, ay;
-  ax.x = ax.y = a.x;
-  ay.x = ay.y = a.y;
-  acc = __builtin_elementwise_fma(ax, b, acc);
-  return __builtin_elementwise_fma(ay, br, acc);
-}
-MIMO_DEV v2f sic_rot(v2f b) {
-  v2f r;
-  r.x = -b.y;
-  r.y = b.x;
-  return r;
-}
-
-// qam_demap and qam_point of its index in one go: the levels m of both dimensions give the
-// index (gray(mI) << b) | gray(mQ) and the point ((2 m - (L - 1)) scale), as qam_point finds
-// it from gray_dec of the index
-MIMO_DEV uint32_t sic_slice(v2f z, const Qam &q, v2f *point) {
-  const uint32_t mI = qam_level(z.x * q.inv_scale, q.L), mQ = qam_level(z.y * q.inv_scale, q.L);
-  point->x = (float)(int32_t)(2 * mI - (q.L - 1)) * q.scale;
-  point->y = (float)(int32_t)(2 * mQ - (q.L - 1)) * q.scale;
-  return (gray_enc(mI) << q.b) | gray_enc(mQ);
-}
-
-// the LLR image of the soft output
-constexpr int kSicLlrImg = 40 * 1024;   // 3 workgroups per CU beside the index image
-template <int B, bool F32>
-constexpr int sic_llr_bps() { return F32 ? 8 * B : 2 * B; }   // LLR bytes per symbol
-template <int B, bool F32>
-constexpr int sic_llr_rs() { return kSicT * sic_llr_bps<B, F32>() + 16; }   // image row bytes
-template <int N, int B, bool F32>
-constexpr int sic_soft_sc() {
-  int sc = sic_sc<N>();
-  while (sc > 1 && sc * N * sic_llr_rs<B, F32>() > kSicLlrImg) sc /= 2;
-  return sc;
-}
-
-// a symbol's 2 B LLRs into the image: p is aligned as the row's misalignment and the lane
-// stride allow (8 bytes for fp32 and 256-QAM int8, 4 for 16-QAM int8, else 2)
-template <int B, bool F32>
-MIMO_DEV void sic_llr_put(uint8_t *p, const float *v) {
-  if constexpr (F32) {
-#pragma unroll
-    for (int i = 0; i < B; i++)
-      reinterpret_cast<float2 *>(p)[i] = make_float2(v[2 * i], v[2 * i + 1]);
-  } else if constexpr (B == 4) {
-    *reinterpret_cast<uint2 *>(p) = make_uint2(llr_pack4(v), llr_pack4(v + 4));
-  } else if constexpr (B == 2) {
-    *reinterpret_cast<uint32_t *>(p) = llr_pack4(v);
-  } else {
-#pragma unroll
-    for (int i = 0; i < B; i++)
-      reinterpret_cast<uint16_t *>(p)[i] = (uint16_t)(llr_q8(v[2 * i]) | (llr_q8(v[2 * i + 1]) << 8));
-  }
 }
 
 // Soft feedback (FB, mimo_rx_sic_soft_fb): the posterior mean and variance of one stage's symbol

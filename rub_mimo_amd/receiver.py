@@ -331,6 +331,23 @@ class Receiver:
                          llr_scale)
         check(lib().mimo_rx_sic_soft_fb(self._h, C.byref(a), stream), "sic_soft_fb")
 
+    def pic_soft(self, sym, llr, prior=None, out_sym=None, out_idx=None, n_frames=None,
+                 max_out=None, out_layout=0, fmt=_lib.LLR_I8, llr_scale=1.0, prior_scale=1.0,
+                 stream=None):
+        """Soft-input MMSE-PIC detection of the last batch's equalised symbols
+        (mimo_rx_pic_soft; pic.pic_frame is the definition): prior holds int8 a-priori LLRs in
+        llr's int8 shape and layout (natural LLR = value / prior_scale; None = all zero), such
+        as mimo_fec_siso's extrinsic output; llr receives the extrinsic LLRs of the MMSE
+        estimate after every other stream's expected symbol is cancelled, int8 (_lib.LLR_I8) or
+        float32 (_lib.LLR_F32), scaled by llr_scale; out_sym and out_idx optionally receive
+        the estimates and their indices. N = 1, 2, 4. Asynchronous on `stream`; rows the decode
+        did not write get 0."""
+        a = _lib.PicSoft(_ptr(sym), _ptr(prior), _ptr(llr), _ptr(out_sym), _ptr(out_idx),
+                         self._last if n_frames is None else n_frames,
+                         self.params.pid_max if max_out is None else max_out, out_layout, fmt,
+                         llr_scale, prior_scale)
+        check(lib().mimo_rx_pic_soft(self._h, C.byref(a), stream), "pic_soft")
+
     def sic_order(self, n_frames=None):
         """Detection order [n_frames][M_occ][N] (uint8 stream indices, first detected first) of
         the last batch (mimo_rx_sic_order); zero rows for slots that did not sync."""
