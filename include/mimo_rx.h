@@ -439,6 +439,61 @@ typedef struct mimo_pic_soft {
  * the slot count grows, so it can be captured into a graph after one warm-up call. */
 int mimo_rx_pic_soft(mimo_rx *h, const mimo_pic_soft *a, void *hip_stream);
 
+/* ---------------- layered tree search (LORD): near-ML soft detection ----
+ * The one detector here that searches the lattice and does not only filter it: for every target
+ * stream t it enumerates all L^2 values of s_t, detects the other N - 1 streams by hard
+ * successive cancellation under each value, and takes max-log LLRs of s_t's bits over those L^2
+ * candidate vectors. Every bit has both hypotheses in the list (no clipping); at N = 2 the
+ * result is exactly the max-log ML detector's. No priors and no z output. Opt-in and after the
+ * batch; unless stated otherwise the conditions, side-effect rules, shape checks, erased rows,
+ * alignment, asynchrony and graph-capture rules of mimo_rx_sic_soft apply, and it works with
+ * cfo_correct, with frames_per_capture > 1 and after MIMO_STAGES_DECODE.
+ *
+ * Per synced frame and occupied carrier, as in the SIC and PIC sections: G and s2 = noise_var;
+ * Q = G^H G, accumulated in fp64 and stored as fp32; lam = s2 for MMSE, 0 for ZF and for ZF2 at
+ * N = 2; m = (Q + lam I) y, the matched-filter statistic recovered from the decode's y. The
+ * metric of a symbol vector s is D(s) = s^H Q s - 2 Re(s^H m), which is |X - G s|^2 up to a
+ * constant. Per target stream t = 0..N-1:
+ *   1. Order. The other streams by decreasing Q[u][u] are o_0, o_1, ...; the order is decided on
+ *      the stored fp32 values and ties go to the lower index. Permutation
+ *      p = (o_(N-2), ..., o_0, t): the target sits in the last position, o_0 is detected first.
+ *   2. Factor. U upper triangular with a real positive diagonal, U^H U = P (Q + r I) P^T,
+ *      computed per carrier and frame in fp64 from the stored Q and stored as fp32. r = s2
+ *      whatever the detector, like the PIC pass's A; at N = 2, r = 0: there the one sliced
+ *      stream has to be the exact minimiser of D for the result to be the max-log ML
+ *      detector's, and with r = s2 the chain would slice the biased estimate, the minimiser of
+ *      D(s) + s2 |s|^2 (equal for QPSK, not for 16-QAM and up).
+ *   3. Candidates. Per written symbol yt = U^-H (P m). Each of the L^2 values c of s_t, in the
+ *      index order of the decode's slicer, is a candidate: s_(N-1) = c, and for k = N-2 .. 0
+ *      e_k = (yt_k - sum_{j>k} U_kj s_j) / U_kk, s_k = qam_point(the decode's slicer of e_k).
+ *   4. Metric. D_c = sum_k |yt_k - sum_{j>=k} U_kj s_j|^2 - r sum_k |s_k|^2, which is
+ *      D(s) + |yt|^2 for the completed vector; the residuals come out of step 3.
+ *   5. LLR_i(t) = llr_scale (min_{c: bit_i(c) = 1} D_c - min_{c: bit_i(c) = 0} D_c) / s2; bit
+ *      order, positive = bit 0, the formats MIMO_LLR_I8 / MIMO_LLR_F32, the rounding and
+ *      NaN -> 0 are exactly mimo_rx_sic_soft's, and the int8 output is bitwise the rounded and
+ *      clamped fp32 output.
+ *   6. idx_t = the candidate c with the smallest D_c; the lowest c wins a tie.
+ * At N = 1 there is no chain: D_c = Q |c|^2 - 2 Re(c* m), the max-log LLRs of z = m / Q with
+ * error power s2 / Q.
+ *
+ * These get LLR 0 and idx 0, and nothing of them is read: rows the decode did not write,
+ * carriers whose Q or U is not finite, and frames with noise_var <= 0 or not finite.
+ *
+ * MIMO_ERR_ARG: mimo_rx_sic_soft's cases. MIMO_ERR_UNSUPPORTED (mimo_last_error names the pass):
+ * MIMO_DET_SISO, MIMO_DET_ZF2 at N != 2, N = 3 and N = 8. Instances exist for N = 1, 2, 4,
+ * b = 1..4, both layouts, both formats. */
+typedef struct mimo_lord_soft {
+  const void *d_sym;      /* the last batch's d_out_sym */
+  void *d_llr;            /* LLRs, [d_sym's rows][M_occ][2b] int8 or float; required */
+  void *d_out_idx;        /* the best candidate's index per (row, carrier), or NULL */
+  uint32_t n_frames, max_out_syms, out_layout;
+  uint32_t format;        /* MIMO_LLR_I8 / MIMO_LLR_F32, of d_llr */
+  float llr_scale;        /* of d_llr; finite, > 0 */
+} mimo_lord_soft;
+/* Asynchronous on hip_stream (NULL: the handle's), no host synchronisation; allocates only when
+ * the slot count grows, so it can be captured into a graph after one warm-up call. */
+int mimo_rx_lord_soft(mimo_rx *h, const mimo_lord_soft *a, void *hip_stream);
+
 /* ---------------- channel code over the int8 LLR rows: K = 7 Viterbi decoder (absent from the
  * reference: it stops at modem_demodulate and has no channel code) ----
  * An opt-in pass over a buffer of int8 LLRs such as a soft pass's d_llr (MIMO_LLR_I8); it needs

@@ -80,6 +80,12 @@ class PicSoft(C.Structure):
                 ("format", C.c_uint32), ("llr_scale", C.c_float), ("prior_scale", C.c_float)]
 
 
+class LordSoft(C.Structure):
+    _fields_ = [("d_sym", C.c_void_p), ("d_llr", C.c_void_p), ("d_out_idx", C.c_void_p),
+                ("n_frames", C.c_uint32), ("max_out_syms", C.c_uint32),
+                ("out_layout", C.c_uint32), ("format", C.c_uint32), ("llr_scale", C.c_float)]
+
+
 class FecConfig(C.Structure):
     _fields_ = [("rate", C.c_uint32), ("n_c", C.c_uint32), ("perm", C.c_void_p)]
 
@@ -146,6 +152,7 @@ SIGNATURES = {
     "mimo_rx_sic_soft": (C.c_int, [_vp, _P(SicSoft), _vp]),
     "mimo_rx_sic_soft_fb": (C.c_int, [_vp, _P(SicSoft), _vp]),
     "mimo_rx_pic_soft": (C.c_int, [_vp, _P(PicSoft), _vp]),
+    "mimo_rx_lord_soft": (C.c_int, [_vp, _P(LordSoft), _vp]),
     "mimo_rx_sic_order": (C.c_int, [_vp, _vp, _u32]),
     "mimo_rx_sic_mse": (C.c_int, [_vp, _vp, _u32]),
     "mimo_fec_create": (C.c_int, [_P(FecConfig), _P(_vp)]),

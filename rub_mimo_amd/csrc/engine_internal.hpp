@@ -5,6 +5,7 @@
 //   engine_batch.cpp   mimo_rx_process_batch, the HIP-graph cache, batch getters, soft output
 //   engine_sic.cpp     mimo_rx_sic_detect, mimo_rx_sic_soft(_fb) and the getters: the SIC passes
 //   engine_pic.cpp     mimo_rx_pic_soft: the soft-input MMSE-PIC pass
+//   engine_lord.cpp    mimo_rx_lord_soft: the layered tree-search pass
 //   engine_fec.cpp     mimo_fec_*: the channel code's handle, host encoder, Viterbi and
 //                      soft-output decoder launches
 //   engine_stream.cpp  mimo_rx_execute: the streaming framesync state machine, DEBUG_LOG
@@ -208,6 +209,11 @@ struct mimo_rx {
   // flags [F][M_occ] of the last batch
   DevBuf<float> pic_Q;
   DevBuf<uint8_t> pic_ok;
+  // layered tree search (engine_lord.cpp): Q as above, the N factors U [F][N][N^2 + N][M_occ],
+  // the N permutations [F][N][M_occ] and the carrier flags [F][M_occ] of the last batch
+  DevBuf<float> lord_Q, lord_U;
+  DevBuf<uint32_t> lord_perm;
+  DevBuf<uint8_t> lord_ok;
   // ---- streaming state (facade) and debug buffers (in no captured graph) ----
   // The device capture holds samples [origin, origin + total) of the stream since
   // construction/reset (positions inside it are capture-relative).

@@ -451,6 +451,44 @@ struct PicPassArgs {
 // false when (N, bits) has no instance or the batch shape does not fit (nothing launched)
 bool launch_pic_pass(const PicPassArgs &a, uint32_t n_frames, hipStream_t s);
 
+// layered tree-search soft detection (lord_kernels.hip; mimo_rx_lord_soft): per (frame, occupied
+// carrier) Q as above and, per target stream, the permutation and the upper factor U of
+// P (Q + s2 I) P^T; then one pass over the batch's equalised symbols
+constexpr uint32_t lord_u_rows(uint32_t N) { return N * N + N; }   // floats of one target's U
+struct LordTableArgs {
+  uint32_t N, M, M_occ;
+  const int32_t *occ_index;
+  const float2 *G;                 // [F][M][N][N]
+  const FrameInfo *info;
+  float *Q;                        // [F][pic_q_rows(N)][M_occ], PicTableArgs::Q's packing
+  float *U;                        // [F][N targets][lord_u_rows(N)][M_occ]: N diagonal values,
+                                   // their N reciprocals, Re and Im of the entries above it
+  uint32_t *perm;                  // [F][N targets][M_occ]: byte k = the stream at position k
+  uint8_t *ok;                     // [F][M_occ]: 1 when the frame is synced, noise_var > 0 and
+                                   // finite, and Q and every U are finite (all else is erased)
+};
+// false when N has no instance (nothing launched)
+bool launch_lord_tables(const LordTableArgs &a, uint32_t n_frames, hipStream_t s);
+
+struct LordPassArgs {
+  const float2 *sym;               // the batch's d_out_sym
+  uint8_t *out_idx;                // the best candidate's index, same layout, or null
+  void *llr;                       // [sym's rows][M_occ][2 bits] int8 or float
+  uint32_t N, M_occ, max_out;
+  int symbol_major;
+  int mmse;                        // lambda = s2 (MIMO_DET_MMSE) or 0
+  Qam qam;
+  const FrameInfo *info;
+  const float *Q, *U;              // LordTableArgs::Q, ::U
+  const uint32_t *perm;            // LordTableArgs::perm
+  const uint8_t *ok;               // LordTableArgs::ok
+  float llr_scale;
+  int f32;                         // MIMO_LLR_F32
+  uint32_t bits;                   // per dimension (1..4)
+};
+// false when (N, bits) has no instance or the batch shape does not fit (nothing launched)
+bool launch_lord_pass(const LordPassArgs &a, uint32_t n_frames, hipStream_t s);
+
 // K = 7 Viterbi decoder over rows of int8 LLRs (fec_kernels.hip; mimo_fec_decode): one wave per
 // row, lane = state, persistent waves striding over the rows
 constexpr uint32_t kFecChunk = 64;          // trellis steps per decision chunk (one word per lane)

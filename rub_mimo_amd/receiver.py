@@ -348,6 +348,21 @@ class Receiver:
                          llr_scale, prior_scale)
         check(lib().mimo_rx_pic_soft(self._h, C.byref(a), stream), "pic_soft")
 
+    def lord_soft(self, sym, llr, out_idx=None, n_frames=None, max_out=None, out_layout=0,
+                  fmt=_lib.LLR_I8, llr_scale=1.0, stream=None):
+        """Layered tree-search (LORD) soft detection of the last batch's equalised symbols
+        (mimo_rx_lord_soft; lord.lord_frame is the definition): per target stream every value
+        of its symbol is tried, the other streams are detected by hard successive cancellation
+        under each, and llr receives the max-log LLRs over those candidates, int8 (_lib.LLR_I8)
+        or float32 (_lib.LLR_F32), scaled by llr_scale; out_idx optionally receives the best
+        candidate's index. Exactly max-log ML at N = 2. N = 1, 2, 4. Asynchronous on `stream`;
+        rows the decode did not write get 0."""
+        a = _lib.LordSoft(_ptr(sym), _ptr(llr), _ptr(out_idx),
+                          self._last if n_frames is None else n_frames,
+                          self.params.pid_max if max_out is None else max_out, out_layout, fmt,
+                          llr_scale)
+        check(lib().mimo_rx_lord_soft(self._h, C.byref(a), stream), "lord_soft")
+
     def sic_order(self, n_frames=None):
         """Detection order [n_frames][M_occ][N] (uint8 stream indices, first detected first) of
         the last batch (mimo_rx_sic_order); zero rows for slots that did not sync."""
