@@ -208,6 +208,10 @@ int mimo_rx_batch_results(mimo_rx *h, mimo_frame_result *out, uint32_t n_frames)
 int mimo_rx_batch_corr(mimo_rx *h, uint32_t *corr_idx, uint32_t *s0_idx, uint32_t n_frames);
 int mimo_rx_batch_G(mimo_rx *h, float *G, uint32_t n_frames);
 int mimo_rx_batch_W(mimo_rx *h, float *W, uint32_t n_frames);
+/* normalize_gain of every frame slot, [n_frames][M_occ] floats (1 except with MIMO_DET_ZF2 and
+ * MIMO_DET_SISO at 2x2, where it is 1 / |det G|^2; mimo_rx_get_gain reads slot 0 only); rows of
+ * slots that did not sync are not meaningful; a host copy, synchronises */
+int mimo_rx_batch_gain(mimo_rx *h, float *gain, uint32_t n_frames);
 
 /* ---------------- soft output (absent from the reference: main.cc slices to a hard index) ----
  * An opt-in pass after mimo_rx_process_batch (MIMO_STAGES_ALL or _DECODE) over that batch's

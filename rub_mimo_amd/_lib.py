@@ -146,6 +146,7 @@ SIGNATURES = {
     "mimo_rx_batch_corr": (C.c_int, [_vp, _vp, _vp, _u32]),
     "mimo_rx_batch_G": (C.c_int, [_vp, _vp, _u32]),
     "mimo_rx_batch_W": (C.c_int, [_vp, _vp, _u32]),
+    "mimo_rx_batch_gain": (C.c_int, [_vp, _vp, _u32]),
     "mimo_rx_soft_demap": (C.c_int, [_vp, _P(SoftDemap), _vp]),
     "mimo_rx_batch_mse": (C.c_int, [_vp, _vp, _u32]),
     "mimo_rx_sic_detect": (C.c_int, [_vp, _P(SicDetect), _vp]),

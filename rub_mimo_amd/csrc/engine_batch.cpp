@@ -298,6 +298,21 @@ int mimo_rx_batch_W(mimo_rx *h, float *W, uint32_t F) {
   return MIMO_OK;
 }
 
+int mimo_rx_batch_gain(mimo_rx *h, float *gain, uint32_t F) {
+  if (!h || !gain) return fail(MIMO_ERR_ARG, "null argument");
+  if (F > h->last_frames) return fail(MIMO_ERR_ARG, "more frames than the last batch");
+  if (F == 0) return MIMO_OK;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipDeviceSynchronize());
+  std::vector<float> tmp((size_t)F * h->M);
+  HIPCHK(hipMemcpy(tmp.data(), h->ws.gain.p, sizeof(float) * tmp.size(), hipMemcpyDeviceToHost));
+  for (uint32_t f = 0; f < F; f++)
+    for (uint32_t k = 0; k < h->M; k++)
+      if (h->occ_index[k] >= 0)
+        gain[(size_t)f * h->M_occ + h->occ_index[k]] = tmp[(size_t)f * h->M + k];
+  return MIMO_OK;
+}
+
 // ---------------- soft output: post-detection MSE and max-log LLRs (soft_kernels.hip) -------
 // the MSE of the last batch's F frame slots into h->nu, on stream s
 static int launch_batch_mse(mimo_rx *h, uint32_t F, hipStream_t s) {

@@ -268,6 +268,14 @@ class Receiver:
         check(lib().mimo_rx_batch_W(self._h, W.ctypes.data, n), "batch_W")
         return W
 
+    def gain(self, n_frames=None):
+        """normalize_gain [n_frames][M_occ] of the last batch (mimo_rx_batch_gain): 1 except
+        with the 2x2 reference invert (DET_ZF2, DET_SISO), where it is 1 / |det G|^2."""
+        n = self._last if n_frames is None else n_frames
+        g = np.zeros((n, self.M_occ), np.float32)
+        check(lib().mimo_rx_batch_gain(self._h, g.ctypes.data, n), "batch_gain")
+        return g
+
     def soft_demap(self, out_sym, out_llr, n_frames=None, max_out=None, out_layout=0,
                    fmt=_lib.LLR_I8, llr_scale=1.0, stream=None):
         """Max-log LLRs of the last batch's equalised symbols (mimo_rx_soft_demap): out_sym is

@@ -193,6 +193,14 @@ def test_ingest_sc16_argument_errors_without_gpu():
     assert b"stride" in L.mimo_last_error()
 
 
+def test_batch_gain_is_bound_and_refuses_null_arguments():
+    L = _lib.lib()
+    assert "mimo_rx_batch_gain" in _lib.SIGNATURES
+    buf = (C.c_float * 4)()
+    assert L.mimo_rx_batch_gain(None, C.cast(buf, C.c_void_p), 1) == -1
+    assert b"null" in L.mimo_last_error()
+
+
 def test_cfo_argument_errors_without_gpu():
     L = _lib.lib()
     eps = (C.c_double * 3)()

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import decode_support as ds
 from oracle import codes, ref
 from rub_mimo_amd import _lib
 from rub_mimo_amd import framing as fr
@@ -546,20 +547,24 @@ def test_framegen_matches_oracle_tx():
 
 
 def _c_frame_parity(M, cp, N, nac, pid, qam, det, snr, seed, bias=True, max_delta=SYM_TOL,
-                    search_mode=0, path=None, out_idx=False, ff_margin=None):
+                    search_mode=0, path=None, out_idx=False, ff_margin=None, sct=None):
+    """sct: the subcarrier allocation (_sctype: None, "liquid" or "all"), given to the
+    synthesiser, the receiver and the oracle."""
+    p = _sctype(M, sct)
     S = Synthesizer(SynthParams(M=M, cp_len=cp, num_streams=N, num_access_codes=nac, pid=pid,
-                                qam_order=qam, seed=seed, snr_db=snr))
+                                qam_order=qam, seed=seed, snr_db=snr, p=p))
     L = S.frame_len(0)
+    P = RxParams(M=M, cp_len=cp, num_streams=N, num_access_codes=nac, pid_max=pid,
+                 detector=det, keep_identity_bias=bias, qam_order=qam, p=p)
+    rxo = Receiver(P)
+    mocc = rxo.M_occ
     out = _lib.DeviceBuffer(N * L * 8)
-    tx = _lib.DeviceBuffer(N * pid * M)
+    tx = _lib.DeviceBuffer(N * pid * mocc)
     S.generate(out, L, L, 1, tx_idx=tx)
     rx = out.download(np.complex64, N * L).reshape(N, L)
-    txi = tx.download(np.uint8, N * pid * M).reshape(N, pid, M)
-    P = RxParams(M=M, cp_len=cp, num_streams=N, num_access_codes=nac, pid_max=pid,
-                 detector=det, keep_identity_bias=bias, qam_order=qam)
-    rxo = Receiver(P)
-    osym = _lib.DeviceBuffer(N * pid * M * 8)
-    oidx = _lib.DeviceBuffer(N * pid * M) if out_idx else None
+    txi = tx.download(np.uint8, N * pid * mocc).reshape(N, pid, mocc)
+    osym = _lib.DeviceBuffer(N * pid * mocc * 8)
+    oidx = _lib.DeviceBuffer(N * pid * mocc) if out_idx else None
     rxo.process(out, L, L, 1, max_out=pid, out_sym=osym, out_idx=oidx, ref_mode=2,
                 ref_seed=seed, frame_id0=0)
     r = rxo.results()[0]
@@ -567,7 +572,7 @@ def _c_frame_parity(M, cp, N, nac, pid, qam, det, snr, seed, bias=True, max_delt
         assert rxo.decode_path() == path, (rxo.decode_path(), path)
     ci, si = rxo.corr()
     o = ref.FrameSyncRef(M, cp, N, nac, pid_max=pid, detector=det, keep_identity_bias=bias,
-                         trace_corr=True, search_mode=search_mode)
+                         trace_corr=True, search_mode=search_mode, p=p)
     if ff_margin is None:
         assert o.execute(rx) == ref.STATE_MIMO
     else:
@@ -602,25 +607,32 @@ def _c_frame_parity(M, cp, N, nac, pid, qam, det, snr, seed, bias=True, max_delt
             if tr[-1] > (1 + 1e-3) * tr[-2]:
                 assert ci[0, rr, ac] == oci[rr, ac], (rr, ac)
     syms_o = o.symbols()[:pid]
-    ours = osym.download(np.complex64, N * pid * M).reshape(N, pid, M).transpose(1, 0, 2)
+    ours = osym.download(np.complex64, N * pid * mocc).reshape(N, pid, mocc).transpose(1, 0, 2)
     d = evm_delta(ours, syms_o)
     assert d <= max_delta, d
+    # and element by element: every symbol within DEC_UNITS float32 roundings (at that element)
+    # of the float64 decode of this capture with the handle's own W, gain and corr indices
+    assert r["n_sym"] >= pid
+    y64, u = ds.decode_reference(rx, rxo.W()[0], rxo.gain()[0], ci[0], r["sync_index"], rxo.p,
+                                 cp, nac, pid)
+    elements = ds.ElementCheck(qam)
     dec_o, num, den, err = ref.demap_evm(syms_o, qam, txi)
     edb_gpu = 10 * np.log10(r["evm_num"] / r["evm_den"])
     edb_ref = 10 * np.log10(num / den)
     assert np.abs(edb_gpu - edb_ref).max() <= EVM_DB_TOL, (edb_gpu, edb_ref)
     if out_idx:
         # hard decisions equal the oracle's except where its symbol sits within 1e-3 of a
-        # decision boundary; the symbol-error counts likewise
-        got = oidx.download(np.uint8, N * pid * M).reshape(N, pid, M)
+        # decision boundary (level units), each mismatch judged on its own; the symbol-error
+        # counts likewise
+        got = oidx.download(np.uint8, N * pid * mocc).reshape(N, pid, mocc)
         mism = got != dec_o
-        if mism.any():
-            y = syms_o.transpose(1, 0, 2)[mism]
-            Lq = int(np.sqrt(qam))
-            sc = np.sqrt(2 * (Lq * Lq - 1) / 3.0)
-            v = np.concatenate([(y.real * sc + Lq) / 2, (y.imag * sc + Lq) / 2])
-            assert np.min(np.abs(v - np.round(v))) < 1e-3
+        bad, _ = ds.index_mismatches(got.transpose(1, 0, 2), syms_o, qam, 1e-3)
+        assert not bad.any(), (int(bad.sum()), int(mism.sum()))
         assert np.abs(r["errors"] - err.astype(np.int64)).max() <= int(mism.sum())
+        elements.frame(y64, u, y=ours, idx=got.transpose(1, 0, 2))
+    else:
+        elements.frame(y64, u, y=ours)
+    elements.finish()
     return d, edb_gpu
 
 
@@ -633,6 +645,13 @@ def test_c2_2x2_zf_1024_16qam_full_frame():
     """BASELINE config C2 at full size (PID 1000, the streaming decode's 2x2 form)."""
     d, e = _c_frame_parity(1024, 76, 2, 20, 1000, 16, _lib.DET_ZF2, 25.0, seed=22)
     assert np.all(e < -15)
+
+
+def test_reg_decode_guard_band_matches_oracle():
+    """decode_reg_kernel<10, 2> against the oracle: C2's geometry with the liquid guard-band and
+    pilot allocation, which the streaming decode refuses (it needs every subcarrier occupied)."""
+    _c_frame_parity(1024, 76, 2, 2, 12, 16, _lib.DET_ZF2, 25.0, seed=23, sct="liquid",
+                    path=_lib.DECODE_SYMBOL, out_idx=True)
 
 
 def test_block_search_form_matches_oracle():
