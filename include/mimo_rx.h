@@ -621,6 +621,40 @@ typedef struct mimo_fec_siso_args {
 } mimo_fec_siso_args;
 int mimo_fec_siso(mimo_fec *f, const mimo_fec_siso_args *a, void *hip_stream);
 
+/* ---- the encoder on the device, with the bit mapper: the transmit side of the same code ----
+ * Same code, rates, rows, perm, geometry and mimo_fec handle as mimo_fec_decode. Integer
+ * arithmetic: the output is defined to the bit.
+ *
+ * Per row, row[0..n_c) is mimo_fec_encode applied to the info bits k = 0..n_info-1, bit k read at
+ * byte k >> 3 with mask 0x80 >> (k & 7) of d_info + row bits_pitch: the format mimo_fec_decode
+ * and mimo_fec_siso write to d_bits. The rest of d_info up to bits_pitch, the low bits of the
+ * last info byte included, is ignored whatever it holds.
+ *   MIMO_FEC_ENC_BITS writes row: all n_c bytes, 0 at positions no coded bit refers to.
+ *   MIMO_FEC_ENC_QAM writes idx[j] = sum over i < 2b of row[2b j + i] << (2b - 1 - i), the
+ *     inverse of the order in which the soft passes write a carrier's 2b LLRs (values 0..b-1 are
+ *     Re, MSB first, then Im; the index is (gray(mI) << b) | gray(mQ)). With n_c = M_occ 2b a
+ *     QAM row is one [M_occ] row of d_tx_idx, and n_rows = F N pid rows are a whole
+ *     [F][N][pid][M_occ] payload of mimo_synth_frames_payload.
+ *
+ * Alignment, pitch rules, error codes, asynchrony and threading are those of mimo_fec_decode:
+ * MIMO_ERR_ARG for a null f, a, d_info or d_out, a pointer that is not 16-byte aligned,
+ * n_rows = 0, a bad bits_pitch, a bad form, qam_bits outside 1..4 with QAM or non-zero with
+ * BITS, n_c not a multiple of 2b, and overlapping d_info and d_out; all checked before anything
+ * touches the GPU. The first call of a handle creates the encoder's own device table (the
+ * inverse position map, n_c uint16); later calls allocate nothing and can be captured into a
+ * graph. The encoder shares no workspace with the decoders, so an encode and a decode of one
+ * handle may be in flight together. */
+enum { MIMO_FEC_ENC_BITS = 0, MIMO_FEC_ENC_QAM = 1 };
+typedef struct mimo_fec_encode_args {
+  const void *d_info;   /* [n_rows][bits_pitch] uint8, info bits packed MSB first */
+  void *d_out;          /* BITS: [n_rows][n_c] uint8, 0/1 at row positions
+                           QAM:  [n_rows][n_c / (2 b)] uint8 QAM indices */
+  uint32_t n_rows, bits_pitch;
+  uint32_t form;        /* MIMO_FEC_ENC_* */
+  uint32_t qam_bits;    /* b = 1..4 with QAM (n_c must be a multiple of 2 b); 0 with BITS */
+} mimo_fec_encode_args;
+int mimo_fec_encode_rows(mimo_fec *f, const mimo_fec_encode_args *a, void *hip_stream);
+
 /* stage timing with HIP events on the handle's launch stream (for the roofline line).
  * stages: 0 S&C, 1 plateau, 2 search, 3 LS, 4 weights, 5 decode, 6 EVM reduce; an sc16 batch
  * that is widened internally (not read in place) adds its widening launch to stage 0 */
@@ -704,6 +738,14 @@ int mimo_synth_frame_len(const mimo_synth_config *c, uint64_t frame_id, uint64_t
 int mimo_synth_frames(const mimo_synth_config *c, uint64_t frame_id0, uint32_t n_frames,
                       void *d_out, uint64_t stride, uint64_t frame_len, void *d_tx_idx,
                       void *d_H, void *hip_stream);
+/* mimo_synth_frames in every respect (offset, sync words, channel, noise, frame grouping, error
+ * codes) with the caller's data symbols: qam_point(d_tx_idx[...] & (L^2 - 1)) for the input
+ * d_tx_idx [F][N][pid][M_occ] uint8, in place of the hash draw. Fed the d_tx_idx that
+ * mimo_synth_frames wrote, it writes the same capture bit for bit. MIMO_ERR_ARG for a null
+ * d_tx_idx unless pid = 0. */
+int mimo_synth_frames_payload(const mimo_synth_config *c, uint64_t frame_id0, uint32_t n_frames,
+                              void *d_out, uint64_t stride, uint64_t frame_len,
+                              const void *d_tx_idx, void *d_H, void *hip_stream);
 
 /* ---------------- helpers (setup-time, host) ---------------- */
 int mimo_sctype_default(uint8_t *p, uint32_t M);   /* ofdmframe_init_default_sctype */

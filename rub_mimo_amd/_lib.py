@@ -32,6 +32,8 @@ LLR_I8, LLR_F32 = 0, 1
 FEC_R12, FEC_R23, FEC_R34 = 0, 1, 2
 # mimo_fec_siso_args.mode: a-posteriori or extrinsic LLRs of the coded bits
 FEC_SISO_APP, FEC_SISO_EXT = 0, 1
+# mimo_fec_encode_args.form: coded rows as 0/1 bytes, or mapped to QAM indices
+FEC_ENC_BITS, FEC_ENC_QAM = 0, 1
 
 
 class RxConfig(C.Structure):
@@ -111,6 +113,11 @@ class FrameResult(C.Structure):
                 ("origin", C.c_uint64), ("capture", C.c_uint32), ("ref_frame", C.c_uint32)]
 
 
+class FecEncodeArgs(C.Structure):
+    _fields_ = [("d_info", C.c_void_p), ("d_out", C.c_void_p), ("n_rows", C.c_uint32),
+                ("bits_pitch", C.c_uint32), ("form", C.c_uint32), ("qam_bits", C.c_uint32)]
+
+
 class SynthConfig(C.Structure):
     _fields_ = [("M", C.c_uint32), ("cp_len", C.c_uint32), ("num_streams", C.c_uint32),
                 ("num_access_codes", C.c_uint32), ("pid", C.c_uint32), ("qam_order", C.c_uint32),
@@ -162,6 +169,7 @@ SIGNATURES = {
     "mimo_fec_encode": (C.c_int, [_vp, _vp, _vp]),
     "mimo_fec_decode": (C.c_int, [_vp, _P(FecDecodeArgs), _vp]),
     "mimo_fec_siso": (C.c_int, [_vp, _P(FecSisoArgs), _vp]),
+    "mimo_fec_encode_rows": (C.c_int, [_vp, _P(FecEncodeArgs), _vp]),
     "mimo_rx_set_timing": (C.c_int, [_vp, C.c_int]),
     "mimo_rx_get_stage_times": (C.c_int, [_vp, _P(C.c_double), _P(_u32)]),
     "mimo_rx_get_sc_exact_count": (C.c_int, [_vp, _P(_u64)]),
@@ -179,6 +187,8 @@ SIGNATURES = {
     "mimo_tx_get_codes": (C.c_int, [_vp, _vp, _vp]),
     "mimo_synth_frame_len": (C.c_int, [_P(SynthConfig), _u64, _P(_u64)]),
     "mimo_synth_frames": (C.c_int, [_P(SynthConfig), _u64, _u32, _vp, _u64, _u64, _vp, _vp, _vp]),
+    "mimo_synth_frames_payload": (C.c_int, [_P(SynthConfig), _u64, _u32, _vp, _u64, _u64, _vp, _vp,
+                                            _vp]),
     "mimo_sctype_default": (C.c_int, [_vp, _u32]),
     "mimo_sctype_liquid": (C.c_int, [_vp, _u32]),
     "mimo_sctype_validate": (C.c_int, [_vp, _u32, _P(_u32), _P(_u32), _P(_u32)]),

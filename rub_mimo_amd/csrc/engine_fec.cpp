@@ -1,7 +1,8 @@
 // rub_mimo_amd/csrc/engine_fec.cpp -- the channel code over the int8 LLR rows: the mimo_fec
 // handle (geometry, position table, host encoder), mimo_fec_decode, the launch of the
 // wave-per-row Viterbi decoder (fec_kernels.hip), and mimo_fec_siso, the launch of the
-// max-log-MAP decoder on the same grid (fec_siso_kernels.hip). Independent of mimo_rx: opt-in
+// max-log-MAP decoder on the same grid (fec_siso_kernels.hip), and mimo_fec_encode_rows, the
+// launch of the encoder and bit mapper (fec_enc_kernels.hip). Independent of mimo_rx: opt-in
 // passes over a buffer of LLRs that the batch launches nothing for. create, geometry, encode and
 // destroy touch no GPU.
 #include <new>
@@ -23,6 +24,10 @@ struct mimo_fec {
   uint32_t siso_blocks = 0;
   // [siso_blocks * waves per block][(chunks + kFecChunk) * kFecChunk]
   DevBuf<int32_t> ws_siso;
+  // ---- created by the first mimo_fec_encode_rows (the encoder's own: no decoder state) ----
+  uint32_t enc_blocks = 0;         // the most workgroups a launch uses
+  std::vector<uint16_t> inv;       // [n_c] the inverse position map (FecEncArgs::inv)
+  DevBuf<uint16_t> d_inv;
 };
 
 namespace {
@@ -91,6 +96,33 @@ int fec_first_siso(mimo_fec *f, hipStream_t s) {
     return fail(MIMO_ERR_NOMEM, "soft-output decoder checkpoint workspace");
   }
   f->siso_blocks = f->grid_blocks;
+  return MIMO_OK;
+}
+
+// workgroups per CU the encoder's grid is sized for: 6 KiB of LDS and 256 threads each
+constexpr uint32_t kFecEncBlocksPerCu = 8;
+
+// the encoder's grid and the inverse position map: row position -> where the kernel parks the
+// parity that belongs there
+int fec_first_encode(mimo_fec *f, hipStream_t s) {
+  int dev = 0, ncu = 0;
+  HIPCHK(hipGetDevice(&dev));
+  HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+  if (ncu <= 0) return fail(MIMO_ERR_HIP, "no CU count");
+  const uint32_t nw = (f->T + 31) / 32;
+  f->inv.assign(f->n_c, (uint16_t)(64 * nw));
+  for (uint32_t t = 0; t < f->T; t++) {
+    const uint32_t pa = f->pos[t] & 0xFFFFu, pb = f->pos[t] >> 16;
+    if (pa != kFecPunctured) f->inv[pa] = (uint16_t)t;
+    if (pb != kFecPunctured) f->inv[pb] = (uint16_t)(32 * nw + t);
+  }
+  if (f->d_inv.ensure(f->inv.size()) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(MIMO_ERR_NOMEM, "encoder position map");
+  }
+  HIPCHK(hipMemcpyAsync(f->d_inv.p, f->inv.data(), sizeof(uint16_t) * f->inv.size(),
+                        hipMemcpyHostToDevice, s));
+  f->enc_blocks = (uint32_t)ncu * kFecEncBlocksPerCu;
   return MIMO_OK;
 }
 
@@ -182,6 +214,47 @@ int mimo_fec_decode(mimo_fec *f, const mimo_fec_decode_args *a, void *hip_stream
   k.pitch_dw = a->bits_pitch / 4;
   const uint32_t wpb = kFecBlock / 64;
   launch_fec_viterbi(k, std::min(f->max_blocks, (a->n_rows + wpb - 1) / wpb), s);
+  HIPCHK(hipGetLastError());
+  return MIMO_OK;
+}
+
+int mimo_fec_encode_rows(mimo_fec *f, const mimo_fec_encode_args *a, void *hip_stream) {
+  if (!f || !a || !a->d_info || !a->d_out) return fail(MIMO_ERR_ARG, "null argument");
+  if (((uintptr_t)a->d_info & 15u) || ((uintptr_t)a->d_out & 15u))
+    return fail(MIMO_ERR_ARG, "d_info and d_out must be 16-byte aligned");
+  if (a->n_rows == 0) return fail(MIMO_ERR_ARG, "n_rows is 0");
+  if ((a->bits_pitch & 3u) || a->bits_pitch < (f->n_info + 7) / 8)
+    return fail(MIMO_ERR_ARG, "bits_pitch must be a multiple of 4 and >= ceil(n_info / 8)");
+  uint32_t group = 1;
+  if (a->form == MIMO_FEC_ENC_BITS) {
+    if (a->qam_bits != 0) return fail(MIMO_ERR_ARG, "qam_bits must be 0 with MIMO_FEC_ENC_BITS");
+  } else if (a->form == MIMO_FEC_ENC_QAM) {
+    if (a->qam_bits < 1 || a->qam_bits > 4)
+      return fail(MIMO_ERR_ARG, "qam_bits must be 1..4 with MIMO_FEC_ENC_QAM");
+    group = 2 * a->qam_bits;
+    if (f->n_c % group) return fail(MIMO_ERR_ARG, "n_c is not a multiple of 2 qam_bits");
+  } else {
+    return fail(MIMO_ERR_ARG, "form must be MIMO_FEC_ENC_BITS or MIMO_FEC_ENC_QAM");
+  }
+  const uint32_t n_out = f->n_c / group;
+  {
+    const uintptr_t i = (uintptr_t)a->d_info, o = (uintptr_t)a->d_out;
+    const uintptr_t ib = (uintptr_t)a->n_rows * a->bits_pitch, ob = (uintptr_t)a->n_rows * n_out;
+    if (i < o + ob && o < i + ib) return fail(MIMO_ERR_ARG, "d_out overlaps d_info");
+  }
+  hipStream_t s = (hipStream_t)hip_stream;
+  if (f->enc_blocks == 0) {
+    const int rc = fec_first_encode(f, s);
+    if (rc) return rc;
+  }
+  FecEncArgs k{};
+  k.info = reinterpret_cast<const uint8_t *>(a->d_info);
+  k.out = reinterpret_cast<uint8_t *>(a->d_out);
+  k.inv = f->d_inv.p;
+  k.n_rows = a->n_rows; k.pitch = a->bits_pitch; k.n_info = f->n_info;
+  k.nw = (f->T + 31) / 32; k.n_out = n_out;
+  if (!launch_fec_encode(k, group, std::min(f->enc_blocks, a->n_rows), s))
+    return fail(MIMO_ERR_UNSUPPORTED, "no encoder instance for this row");
   HIPCHK(hipGetLastError());
   return MIMO_OK;
 }

@@ -134,9 +134,11 @@ int mimo_synth_frame_len(const mimo_synth_config *c, uint64_t frame_id, uint64_t
   return MIMO_OK;
 }
 
-int mimo_synth_frames(const mimo_synth_config *c, uint64_t frame_id0, uint32_t n_frames,
-                      void *d_out, uint64_t stride, uint64_t frame_len, void *d_tx_idx,
-                      void *d_H, void *hip_stream) {
+// the synthesiser: the data symbols are the caller's indices (idx_in) or the hash draw, which
+// tx_idx (optional) receives
+static int synth_frames(const mimo_synth_config *c, uint64_t frame_id0, uint32_t n_frames,
+                        void *d_out, uint64_t stride, uint64_t frame_len, void *d_tx_idx,
+                        const void *d_idx_in, void *d_H, void *hip_stream) {
   if (!c || !d_out || !c->p || !c->s0_bits || !c->s1_bits)
     return fail(MIMO_ERR_ARG, "null argument");
   const int l2 = ilog2(c->M);
@@ -177,8 +179,9 @@ int mimo_synth_frames(const mimo_synth_config *c, uint64_t frame_id0, uint32_t n
       a.dn = 1.0f / sqrtf((float)M_occ); a.gain = 0.25f;
       a.occ_list = docc.p; a.in = nullptr; a.n_sym = c->pid; a.seed = c->seed;
       a.frame_id0 = frame_id0 + f0; a.qam = qam;
-      a.tx_idx = d_tx_idx ? reinterpret_cast<uint8_t *>(d_tx_idx) + (size_t)f0 * N * c->pid * M_occ
-                          : nullptr;
+      const size_t idx0 = (size_t)f0 * N * c->pid * M_occ;
+      a.tx_idx = d_tx_idx ? reinterpret_cast<uint8_t *>(d_tx_idx) + idx0 : nullptr;
+      a.idx_in = d_idx_in ? reinterpret_cast<const uint8_t *>(d_idx_in) + idx0 : nullptr;
       a.out = scratch.p; a.tw = tw;
       launch_tx_symbols(a, l2, nf, s);
     }
@@ -195,6 +198,21 @@ int mimo_synth_frames(const mimo_synth_config *c, uint64_t frame_id0, uint32_t n
     HIPCHK(hipStreamSynchronize(s));
   }
   return MIMO_OK;
+}
+
+int mimo_synth_frames(const mimo_synth_config *c, uint64_t frame_id0, uint32_t n_frames,
+                      void *d_out, uint64_t stride, uint64_t frame_len, void *d_tx_idx,
+                      void *d_H, void *hip_stream) {
+  return synth_frames(c, frame_id0, n_frames, d_out, stride, frame_len, d_tx_idx, nullptr, d_H,
+                      hip_stream);
+}
+
+int mimo_synth_frames_payload(const mimo_synth_config *c, uint64_t frame_id0, uint32_t n_frames,
+                              void *d_out, uint64_t stride, uint64_t frame_len,
+                              const void *d_tx_idx, void *d_H, void *hip_stream) {
+  if (c && c->pid && !d_tx_idx) return fail(MIMO_ERR_ARG, "d_tx_idx is null with pid > 0");
+  return synth_frames(c, frame_id0, n_frames, d_out, stride, frame_len, nullptr, d_tx_idx, d_H,
+                      hip_stream);
 }
 
 // ---------------- helpers ----------------

@@ -523,6 +523,24 @@ struct FecSisoArgs {
 // blocks <= the grid the workspace was sized for
 void launch_fec_siso(const FecSisoArgs &a, uint32_t blocks, hipStream_t s);
 
+// K = 7 encoder and bit mapper over rows of packed info bits (fec_enc_kernels.hip;
+// mimo_fec_encode_rows): one workgroup per row, by output position
+constexpr uint32_t kFecEncBlock = 256;
+constexpr uint32_t kFecEncMaxWords = 768;   // 32-step words of the longest row (T = 24576)
+struct FecEncArgs {
+  const uint8_t *info;             // [n_rows][pitch] info bits packed MSB first
+  uint8_t *out;                    // [n_rows][n_out]
+  // [n_out group] per row position: t for A_t, 32 nw + t for B_t, 64 nw where no coded bit
+  // refers to the position
+  const uint16_t *inv;
+  uint32_t n_rows, pitch, n_info;
+  uint32_t nw;                     // ceil(T / 32) <= kFecEncMaxWords
+  uint32_t n_out;                  // output bytes per row: n_c / group
+};
+// group: row positions per output byte, 1 (0/1 bytes) or 2b (QAM indices). false when there is
+// no instance for it or the row is too long (nothing launched)
+bool launch_fec_encode(const FecEncArgs &a, uint32_t group, uint32_t blocks, hipStream_t s);
+
 // code tables: S0/S1 -> IFFT*dn (framing.cc:1054-1111, 1214-1262) -> zero-pad FFT_F
 struct CodesArgs {
   uint32_t M, N, nac, n_slots;
@@ -543,8 +561,10 @@ struct TxSymArgs {
   float dn;                        // 1/sqrtf(M_pilot+M_data) (framing.cc:115)
   float gain;                      // baseband gain (1 for framegen, 0.25 in tx_worker)
   const int32_t *occ_list;         // [M_occ] -> sc
-  // symbol source: explicit (in != null) [N][n_sym][M_occ] or hashed QAM
+  // symbol source: explicit (in != null) [N][n_sym][M_occ], the caller's QAM indices
+  // (idx_in != null) [F][N][n_sym][M_occ], or hashed QAM
   const float2 *in;
+  const uint8_t *idx_in;
   uint32_t n_sym;
   uint64_t seed, frame_id0;
   Qam qam;

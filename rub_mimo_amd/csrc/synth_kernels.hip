@@ -2,8 +2,9 @@
 //
 // tx_symbols_kernel: framegen::assemble_mimo_packet (framing.cc:210-235) for many symbols at
 //   once: occupied-carrier mapping, unnormalised IFFT, x dft_normalizer (1/sqrt(M_occ)),
-//   cyclic prefix, x baseband gain (main.cc:1048-1053). Symbols come from the caller or
-//   from the counter-based hash (uniform QAM indices, the bench's synthetic data).
+//   cyclic prefix, x baseband gain (main.cc:1048-1053). Symbols come from the caller, as
+//   points or as QAM indices (mimo_synth_frames_payload), or from the counter-based hash
+//   (uniform QAM indices, the bench's synthetic data).
 // mix_kernel: the tx_worker frame layout (main.cc:937-1153) -- zeros, sync words
 //   (framing.cc:169-208), data, zeros -- through a flat Rayleigh channel plus AWGN.
 #include "fft.hpp"
@@ -27,6 +28,8 @@ __global__ __launch_bounds__(T) void tx_symbols_kernel(TxSymArgs a) {
     float2 v;
     if (a.in) {
       v = a.in[((uint64_t)t * a.n_sym + sym) * a.M_occ + j];
+    } else if (a.idx_in) {
+      v = qam_point((uint32_t)a.idx_in[sbase + j] & (uint32_t)(a.qam.L * a.qam.L - 1), a.qam);
     } else {
       const uint32_t idx = (uint32_t)(hash5(a.seed, DOM_DATA, frame_id, t,
                                             (uint64_t)sym * a.M_occ + j) &

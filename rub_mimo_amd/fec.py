@@ -35,6 +35,12 @@ beta_(t+1)(s) and Lambda = M(0) - M(1). d_out receives clamp(Lambda, +-127) (APP
 clamp(Lambda - L_in, +-127) (EXT) at the row position of every kept coded bit and nothing
 elsewhere; info bit k is Lambda_k^u < 0 (a tie gives 0), the info LLR clamp(Lambda_k^u, +-127),
 the metric alpha_T(0), which is the Viterbi metric.
+
+Encoder on the device (mimo_fec_encode_rows, DESIGN.md "Coded transmit"): encode_rows is what it
+writes, from info bits in the packed format above (unpack_bits; whatever lies past bit n_info is
+ignored): the rows of encode (ENC_BITS), or those rows through rows_to_idx (ENC_QAM):
+idx[j] = sum over i < 2b of row[2b j + i] << (2b - 1 - i), the inverse of the order in which the
+soft passes write a carrier's 2b LLRs.
 """
 from __future__ import annotations
 
@@ -193,6 +199,13 @@ def pack_bits(bits, pitch=None):
     return out
 
 
+def unpack_bits(packed, n_info):
+    """[rows][pitch] uint8 in the d_bits format -> bits [rows][n_info] of 0/1; whatever the
+    rows hold past bit n_info is dropped."""
+    packed = np.ascontiguousarray(packed, np.uint8)
+    return np.unpackbits(packed, axis=1, bitorder="big")[:, :n_info]
+
+
 def decode(rate, n_c, llr, perm=None, bits_pitch=None):
     """llr [rows][n_c] int8 -> (packed bits [rows][bits_pitch] uint8, metric [rows] int32):
     what mimo_fec_decode writes."""
@@ -278,10 +291,60 @@ def qam_indices(row, n_bits):
     return (g * w).sum(-1).astype(np.uint8)
 
 
+def rows_to_idx(row, b):
+    """Coded rows [..., n_c] of 0/1 -> QAM indices [..., n_c / (2 b)] uint8, b bits per dimension:
+    idx[j] = sum over i < 2b of row[2b j + i] << (2b - 1 - i), what MIMO_FEC_ENC_QAM writes. Row
+    position i of carrier j is bit 2b - 1 - i of the index (gray(mI) << b) | gray(mQ): values
+    0..b-1 are Re, MSB first, then Im, the order of a carrier's 2b LLRs."""
+    if b not in (1, 2, 3, 4) or np.shape(row)[-1] % (2 * b):
+        raise ValueError("b must be 1..4 and n_c a multiple of 2 b")
+    return qam_indices(row, 2 * b)
+
+
+def idx_to_rows(idx, b):
+    """QAM indices [..., n] -> coded rows [..., n 2b] of 0/1: the inverse of rows_to_idx (bits of
+    the index above 2b are dropped)."""
+    if b not in (1, 2, 3, 4):
+        raise ValueError("b must be 1..4")
+    idx = np.asarray(idx).astype(np.uint32)
+    sh = np.arange(2 * b - 1, -1, -1, dtype=np.uint32)
+    bits = (idx[..., None] >> sh) & 1
+    return bits.reshape(idx.shape[:-1] + (idx.shape[-1] * 2 * b,)).astype(np.uint8)
+
+
+def idx_to_points(idx, b):
+    """QAM indices -> the constellation points qam_point gives them (complex128): the index is
+    (gray(mI) << b) | gray(mQ) and level m is soft.qam_levels(4^b)[m]."""
+    from . import soft
+    idx = np.asarray(idx).astype(np.int64) & ((1 << (2 * b)) - 1)
+    m = np.arange(1 << b)
+    level_of_gray = np.empty(1 << b, np.int64)
+    level_of_gray[m ^ (m >> 1)] = m
+    lv = soft.qam_levels(1 << (2 * b))
+    return lv[level_of_gray[idx >> b]] + 1j * lv[level_of_gray[idx & ((1 << b) - 1)]]
+
+
+ENC_BITS, ENC_QAM = 0, 1
+
+
+def encode_rows(rate, n_c, packed, perm=None, form=ENC_BITS, qam_bits=0):
+    """packed [rows][pitch] uint8 info bits in the d_bits format -> what mimo_fec_encode_rows
+    writes: [rows][n_c] 0/1 bytes (ENC_BITS) or [rows][n_c / (2 b)] QAM indices (ENC_QAM)."""
+    _, n_info, _ = geometry(rate, n_c)
+    row = encode(rate, n_c, unpack_bits(packed, n_info), perm)
+    if form == ENC_BITS:
+        if qam_bits:
+            raise ValueError("qam_bits must be 0 with ENC_BITS")
+        return row
+    if form != ENC_QAM:
+        raise ValueError("form")
+    return rows_to_idx(row, qam_bits)
+
+
 class Fec:
     """One code geometry (mimo_fec_create): rate R12 / R23 / R34, rows of n_c values, an
     optional permutation of n_tx distinct row positions. encode and geometry run on the host;
-    decode runs on the GPU."""
+    decode, siso and encode_rows run on the GPU."""
 
     def __init__(self, rate, n_c, perm=None):
         self._h = None
@@ -327,6 +390,19 @@ class Fec:
         a = _lib.FecDecodeArgs(_ptr(llr), _ptr(bits), _ptr(metric), n_rows,
                                self.min_pitch() if bits_pitch is None else bits_pitch)
         _lib.check(_lib.lib().mimo_fec_decode(self._h, C.byref(a), stream), "mimo_fec_decode")
+
+    def encode_rows(self, info, n_rows, out, form=ENC_BITS, qam_bits=0, bits_pitch=None,
+                    stream=None):
+        """Encode n_rows rows of packed info bits on the device (mimo_fec_encode_rows): info
+        [n_rows][bits_pitch] uint8 in the d_bits format; out receives [n_rows][n_c] 0/1 bytes
+        (ENC_BITS) or [n_rows][n_c / (2 qam_bits)] QAM indices (ENC_QAM). Tensors, DeviceBuffers
+        or addresses. Asynchronous on `stream`."""
+        from .receiver import _ptr
+        a = _lib.FecEncodeArgs(_ptr(info), _ptr(out), n_rows,
+                               self.min_pitch() if bits_pitch is None else bits_pitch, form,
+                               qam_bits)
+        _lib.check(_lib.lib().mimo_fec_encode_rows(self._h, C.byref(a), stream),
+                   "mimo_fec_encode_rows")
 
     def min_info_pitch(self):
         return min_info_pitch(self.n_info)

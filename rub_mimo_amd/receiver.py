@@ -470,6 +470,14 @@ class Synthesizer:
         check(lib().mimo_synth_frames(C.byref(self._cfg), frame_id0, n_frames, _ptr(out), stride,
                                       frame_len, _ptr(tx_idx), _ptr(H), stream), "synth_frames")
 
+    def generate_payload(self, out, stride, frame_len, n_frames, tx_in, frame_id0=0, H=None,
+                         stream=None):
+        """generate() with the caller's data symbols (mimo_synth_frames_payload): tx_in
+        [n_frames][N][pid][M_occ] uint8 QAM indices, e.g. Fec.encode_rows' QAM form."""
+        check(lib().mimo_synth_frames_payload(C.byref(self._cfg), frame_id0, n_frames, _ptr(out),
+                                              stride, frame_len, _ptr(tx_in), _ptr(H), stream),
+              "synth_frames_payload")
+
     def stream_layout(self, n_streams, frames_per_stream, stream0=0):
         """Frame lengths [S][J] of streams that carry the synthesiser's frames
         (stream0+s)*J .. (stream0+s)*J+J-1 back to back, and the common capture length."""
